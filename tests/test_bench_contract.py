@@ -78,3 +78,47 @@ def test_bench_torchrun_tp2_smoke():
     d = json.loads(line)
     assert d["config"]["parallelism"] == "tp2_fsdp2"
     assert d["value"] > 0
+
+
+def _bench_plain(*extra):
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--model", "llama_tiny",
+         "--batch", "2", "--seq", "64", *extra],
+        capture_output=True, text=True, timeout=300,
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+    )
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's loss + parameter sample
+    as float32 .npy, identical run to run (seeded inputs, init and sample);
+    --steps sets the timed step count and --full is accepted."""
+    import numpy as np
+
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    d = _bench_plain("--steps", "3", "--warmup", "1", "--dump-outputs", a)
+    assert d["steps"] == 3 and d["warmup"] == 1
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 * 64 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    _bench_plain("--steps", "3", "--warmup", "1", "--dump-outputs", b, "--full")
+    assert sorted(os.listdir(a)) == ["loss.npy", "params_sample.npy"]
+    total = 0
+    for name in os.listdir(a):
+        xa, xb = np.load(os.path.join(a, name)), np.load(os.path.join(b, name))
+        assert xa.dtype == np.float32 and xa.size > 0
+        assert np.isfinite(xa).all()
+        assert np.array_equal(xa, xb), name
+        total += xa.nbytes
+    # the 64 MB cap for Llama-3-8B rests on arithmetic, not on this tiny
+    # model: 33 units x 65536 sampled elements x 4 B is about 9 MB
+    assert total <= 64 * 2**20
+    assert float(np.load(os.path.join(a, "loss.npy"))[0]) == d["config"]["final_loss"]
+    # one more timed step must change what is dumped
+    c = str(tmp_path / "c")
+    _bench_plain("--steps", "4", "--warmup", "1", "--dump-outputs", c)
+    assert not np.array_equal(np.load(os.path.join(a, "params_sample.npy")),
+                              np.load(os.path.join(c, "params_sample.npy")))

@@ -45,6 +45,62 @@ def test_rmsnorm_fwd_bwd():
 
 
 @requires_gpu
+@pytest.mark.parametrize("rows,hidden", [(3, 4096), (2051, 520)])
+def test_rmsnorm_bwd_dw_repeatable(rows, hidden):
+    """dw is reduced over rows without atomics: repeated calls are bitwise
+    equal (rows > the 1024-block grid cap makes blocks loop over rows; hidden
+    520 leaves most lanes of the 256x8 tile idle), and dw matches an fp64
+    reference to bf16 output rounding (2^-8 relative) plus fp32 error: one
+    rounding per accumulated row, and per term two product roundings and an
+    fp32 rrms (mean over hidden + rsqrt) — (rows+32) * 2^-24 of the column's
+    absolute sum."""
+    from vescale_amd.ops import rmsnorm
+
+    torch.manual_seed(11)
+    x = torch.randn(rows, hidden, device="cuda", dtype=torch.bfloat16)
+    w = torch.randn(hidden, device="cuda", dtype=torch.bfloat16)
+    dy = torch.randn(rows, hidden, device="cuda", dtype=torch.bfloat16)
+
+    def grads():
+        xx, ww = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        rmsnorm(xx, ww, 1e-5).backward(dy)
+        return xx.grad, ww.grad
+
+    dx0, dw0 = grads()
+    for _ in range(4):
+        dx, dw = grads()
+        assert torch.equal(dx, dx0) and torch.equal(dw, dw0)
+
+    xd, dyd = x.double(), dy.double()
+    terms = dyd * xd * torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + 1e-5)
+    ref, abs_sum = terms.sum(0), terms.abs().sum(0)
+    err = (dw0.double() - ref).abs()
+    bound = 2.0 ** -8 * ref.abs() + (rows + 32) * 2.0 ** -24 * abs_sum
+    assert bool((err <= bound).all()), float((err - bound).max())
+
+
+@requires_gpu
+@pytest.mark.parametrize("n", [5, 123457, 2048 * 256 * 8 + 13])
+def test_l2norm_sq_repeatable(n):
+    """Block partials are summed in a fixed order: bitwise equal call to
+    call, for the tail-only case, a multi-block case and one past the
+    2048-block grid cap; fp32 accumulation of positive terms (<= 16 per
+    lane + 8-level block tree + 2048 partials) stays within 1e-5 relative
+    of an fp64 sum."""
+    from vescale_amd.ops import l2norm_sq
+
+    torch.manual_seed(12)
+    for dtype in (torch.bfloat16, torch.float32):
+        x = torch.randn(n, device="cuda", dtype=dtype)
+        got = l2norm_sq(x)
+        assert got.shape == () and got.dtype == torch.float32
+        for _ in range(4):
+            assert torch.equal(l2norm_sq(x), got)
+        ref = x.double().pow(2).sum()
+        assert abs(float(got) - float(ref)) <= 1e-5 * float(ref)
+
+
+@requires_gpu
 def test_rope():
     from vescale_amd.ops import build_rope_table, rope_apply
     from vescale_amd.ops.functional import _rope_ref

@@ -104,7 +104,9 @@ adamw_flat_bf16(unsigned short* __restrict__ param_bf16,
 }
 
 // L2-norm-squared of a flat bf16 or fp32 buffer (for grad clipping):
-// partial per block -> atomicAdd into out[0] (fp32, zero-init by caller).
+// one partial per block -> out[blockIdx.x] (fp32, [gridDim.x]); the caller
+// sums the partials in a fixed order (an fp32 atomicAdd here made the clip
+// scale, and with it every parameter, differ from run to run).
 extern "C" __global__ void __launch_bounds__(BLOCK)
 l2norm_sq_flat(const unsigned short* __restrict__ x_bf16,
                const float* __restrict__ x_f32,
@@ -136,7 +138,7 @@ l2norm_sq_flat(const unsigned short* __restrict__ x_bf16,
     ss += f * f;
   }
   float total = block_reduce_sum<BLOCK>(ss, lds);
-  if (threadIdx.x == 0) atomicAdd(out, total);
+  if (threadIdx.x == 0) out[blockIdx.x] = total;
 }
 
 // in-place scale of a flat buffer (grad clip / loss scale)

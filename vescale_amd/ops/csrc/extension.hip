@@ -58,8 +58,11 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
   TORCH_CHECK(hidden <= 8192, "rmsnorm_bwd supports hidden <= 8192");
   int64_t rows = x.numel() / hidden;
   auto dx = at::empty_like(x);
-  auto dw = at::zeros({hidden}, x.options().dtype(at::kFloat));
+  TORCH_CHECK(hidden % 8 == 0, "hidden must be a multiple of 8");
+  if (rows == 0) return {dx, at::zeros({hidden}, x.options().dtype(at::kFloat))};
   int grid = (int)std::min<int64_t>(rows, 1024);
+  // one dw row per block, summed below in a fixed order (deterministic)
+  auto dw_part = at::empty({grid, hidden}, x.options().dtype(at::kFloat));
   const unsigned short* dres_p = nullptr;
   at::Tensor dres_c;
   if (dres.has_value()) {
@@ -72,8 +75,8 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                      (const unsigned short*)w.data_ptr(),
                      rrms.data_ptr<float>(), dres_p,
                      (unsigned short*)dx.data_ptr(),
-                     dw.data_ptr<float>(), rows, hidden);
-  return {dx, dw};
+                     dw_part.data_ptr<float>(), rows, hidden);
+  return {dx, dw_part.sum(0)};
 }
 
 std::vector<at::Tensor> rmsnorm_res_fwd(at::Tensor x,
@@ -276,16 +279,16 @@ void adamw_step(at::Tensor param, c10::optional<at::Tensor> master,
 }
 
 at::Tensor l2norm_sq(at::Tensor x) {
-  auto out = at::zeros({1}, x.options().dtype(at::kFloat));
   int64_t n = x.numel();
+  int grid = grid_for(n / 8, 256);
+  auto part = at::empty({grid}, x.options().dtype(at::kFloat));
   const unsigned short* xb = nullptr;
   const float* xf = nullptr;
   if (x.scalar_type() == at::kBFloat16) xb = (const unsigned short*)x.data_ptr();
   else xf = x.data_ptr<float>();
-  int grid = grid_for(n / 8, 256);
   hipLaunchKernelGGL(l2norm_sq_flat, dim3(grid), dim3(256), 0, cur_stream(),
-                     xb, xf, out.data_ptr<float>(), n);
-  return out;
+                     xb, xf, part.data_ptr<float>(), n);
+  return part.sum(0, /*keepdim=*/true);
 }
 
 void scale_(at::Tensor x, c10::optional<at::Tensor> scale_t, double scale_c) {

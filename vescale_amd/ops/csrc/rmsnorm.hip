@@ -131,8 +131,10 @@ rmsnorm_res_fwd_bf16(const unsigned short* __restrict__ x,
 // backward:
 //   dx = rrms * w * dy - x * rrms^3/H * sum_j(dy_j * w_j * x_j)
 //   dw = sum_rows(dy * x * rrms)
-// dw accumulated per-block in registers over this block's rows, then one
-// atomicAdd per column into fp32 dw buffer (caller zero-inits).
+// dw accumulated per-block in registers over this block's rows, then
+// stored as row blockIdx.x of the fp32 [gridDim.x, H] partial buffer; the
+// caller reduces the rows (no atomics: fp32 atomicAdd order made dw, and
+// with it the whole train step, differ from run to run).
 extern "C" __global__ void __launch_bounds__(BLOCK)
 rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
                  const unsigned short* __restrict__ x,
@@ -141,7 +143,7 @@ rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
                  const unsigned short* __restrict__ dres,  // nullable:
                  // residual-stream grad added into dx (fused add-backward)
                  unsigned short* __restrict__ dx,
-                 float* __restrict__ dw,  // [H] fp32, zero-init
+                 float* __restrict__ dw_part,  // [gridDim.x, H] fp32
                  int64_t n_rows, int hidden) {
   __shared__ float lds[BLOCK / WAVE];
   const int vec = 8;
@@ -210,13 +212,15 @@ rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
       }
     }
   }
-  // flush dw
+  // flush this block's dw row (plain stores: the host sums the rows in a
+  // fixed order, so dw is bitwise repeatable run to run)
+  float* dwr = dw_part + (int64_t)blockIdx.x * hidden;
   #pragma unroll
   for (int it = 0; it < 4; ++it) {
     int i = (it * BLOCK + threadIdx.x) * vec;
     if (i < hidden) {
 #pragma unroll
-      for (int j = 0; j < vec; ++j) atomicAdd(dw + i + j, dw_acc[it * vec + j]);
+      for (int j = 0; j < vec; ++j) dwr[i + j] = dw_acc[it * vec + j];
     }
   }
 }
