@@ -19,9 +19,13 @@ Autograd: the ring shift is an autograd.Function whose backward shifts
 gradients the OPPOSITE way around the ring; everything else is plain
 differentiable torch, so grads are exact.  Every rank executes the same
 graph, so the reverse-order backward sendrecvs pair up deadlock-free.
-Memory note: this eager CPU/GPU reference keeps per-step activations
-alive for autograd; a flash-style recompute backward is the kernel-level
-follow-up (the HIP flash kernels in ops/csrc cover the dense core).
+Memory note: the default impl="eager" reference keeps per-step
+O(S_local^2) score activations alive for autograd and circulates GQA keys
+and values expanded to Hq heads.  impl="flash" runs every block through
+ops.flash_attention (the general-shape HIP kernel on GPU, its torch
+reference elsewhere), which returns (out, lse) and recomputes scores in
+backward: saved state per ring step is O(S_local * D) — q, the KV block,
+out and lse — and k/v travel the ring with their own Hkv heads.
 
 Causality is exact across blocks: with q-block index i and kv-block
 index j (global offsets i*S_local, j*S_local), j>i contributes nothing
@@ -80,6 +84,42 @@ def _merge(acc, lse, block_out, block_lse):
     return acc, new_lse
 
 
+def _ring_flash(ql, kl, vl, group, p, my, is_causal, scale):
+    """Ring loop over ops.flash_attention blocks.  k/v circulate with their
+    own Hkv heads.  Every rank runs every block (so the shift nodes'
+    backward pairs up); a future block (j > my) is passed with a shift that
+    masks it wholly, and flash_attention's dead-row semantics (out = 0,
+    lse = -inf, zero grads) make it a no-op in the merge.  The running
+    (acc, lse) pair is fp32 and seeded from step 0 — the diagonal block,
+    whose rows are all live — so the merge never sees -inf on both sides."""
+    from ..ops import flash_attention
+
+    s_local = ql.shape[2]
+    k_cur, v_cur = kl, vl
+    acc = lse = None
+    for step in range(p):
+        j = (my - step) % p  # global kv-block index currently held
+        if step != p - 1:
+            k_nxt = _RingShift.apply(k_cur, group)
+            v_nxt = _RingShift.apply(v_cur, group)
+        masked = is_causal and j >= my  # past blocks (j < my) are fully visible
+        block_out, block_lse = flash_attention(
+            ql, k_cur, v_cur,
+            is_causal=masked,
+            causal_shift=(my - j) * s_local if masked else 0,
+            scale=scale, return_lse=True,
+        )
+        block_out = block_out.float()
+        block_lse = block_lse.float().unsqueeze(-1)
+        if step == 0:
+            acc, lse = block_out, block_lse
+        else:
+            acc, lse = _merge(acc, lse, block_out, block_lse)
+        if step != p - 1:
+            k_cur, v_cur = k_nxt, v_nxt
+    return acc.to(ql.dtype)
+
+
 def ring_sdpa(
     q: DTensor,
     k: DTensor,
@@ -88,14 +128,18 @@ def ring_sdpa(
     is_causal: bool = False,
     scale: Optional[float] = None,
     seq_dim: int = 2,
+    impl: str = "eager",
 ) -> DTensor:
     """Exact sequence-parallel attention with ring-circulated KV.
 
     q/k/v: DTensors [B, H, S, D] Shard(seq_dim) on a 1-D mesh; returns
     the same layout.  GQA (fewer KV heads) works: KV heads broadcast over
     the query-head grouping like F.scaled_dot_product_attention with
-    enable_gqa.
+    enable_gqa.  impl="flash" computes each block with ops.flash_attention
+    (see the module docstring's memory note); it needs the default
+    [B, H, S, D] layout (seq_dim == 2).
     """
+    assert impl in ("eager", "flash"), f"unknown impl {impl!r}"
     mesh = q.device_mesh
     assert mesh.ndim == 1, "ring_sdpa runs over a 1-D (SP) mesh"
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -110,6 +154,10 @@ def ring_sdpa(
     B, Hq, Sq, D = ql.shape
     Hk = kl.shape[1]
     assert Hq % Hk == 0, "query heads must be a multiple of kv heads (GQA)"
+    if impl == "flash":
+        assert seq_dim == 2, "impl='flash' needs the [B, H, S, D] layout"
+        out = _ring_flash(ql, kl, vl, group, p, my, is_causal, scale)
+        return DTensor.from_local(out, mesh, [Shard(seq_dim)])
     if Hk != Hq:
         rep = Hq // Hk
         kl = kl.repeat_interleave(rep, dim=1)
@@ -158,10 +206,13 @@ def ring_sdpa(
 class RingAttention(torch.nn.Module):
     """Module wrapper mirroring UlyssesAttention."""
 
-    def __init__(self, *, is_causal: bool = False, scale: Optional[float] = None):
+    def __init__(self, *, is_causal: bool = False, scale: Optional[float] = None,
+                 impl: str = "eager"):
         super().__init__()
         self.is_causal = is_causal
         self.scale = scale
+        self.impl = impl
 
     def forward(self, q: DTensor, k: DTensor, v: DTensor) -> DTensor:
-        return ring_sdpa(q, k, v, is_causal=self.is_causal, scale=self.scale)
+        return ring_sdpa(q, k, v, is_causal=self.is_causal, scale=self.scale,
+                         impl=self.impl)

@@ -42,14 +42,18 @@ def ulysses_sdpa(
     scale: Optional[float] = None,
     seq_dim: int = 2,
     head_dim: int = 1,
+    impl: str = "sdpa",
 ) -> DTensor:
     """Sequence-parallel scaled-dot-product attention.
 
     q/k/v: DTensors of layout [B, H, S, D] (default dims) sharded
     Shard(seq_dim) on a 1-D mesh.  Returns a DTensor sharded the same
     way.  Head-count may differ between q and k/v (GQA) as long as both
-    divide the mesh size.
+    divide the mesh size.  impl="flash" runs the local attention through
+    ops.flash_attention instead of F.scaled_dot_product_attention (needs
+    the default [B, H, S, D] dims).
     """
+    assert impl in ("sdpa", "flash"), f"unknown impl {impl!r}"
     mesh = q.device_mesh
     assert mesh.ndim == 1, "ulysses_sdpa runs over a 1-D (SP) mesh"
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -65,11 +69,17 @@ def ulysses_sdpa(
     vh = v.redistribute(placements=[Shard(head_dim)])
 
     ql, kl, vl = qh.to_local(), kh.to_local(), vh.to_local()
-    o = F.scaled_dot_product_attention(
-        ql, kl, vl,
-        is_causal=is_causal, scale=scale,
-        enable_gqa=(ql.shape[1] != kl.shape[1]),
-    )
+    if impl == "flash":
+        assert (seq_dim, head_dim) == (2, 1), "impl='flash' needs [B, H, S, D]"
+        from ..ops import flash_attention
+
+        o = flash_attention(ql, kl, vl, is_causal=is_causal, scale=scale)
+    else:
+        o = F.scaled_dot_product_attention(
+            ql, kl, vl,
+            is_causal=is_causal, scale=scale,
+            enable_gqa=(ql.shape[1] != kl.shape[1]),
+        )
     oh = DTensor.from_local(o, mesh, [Shard(head_dim)])
     # head -> seq: the fourth all_to_all
     return oh.redistribute(placements=[Shard(seq_dim)])
@@ -79,10 +89,13 @@ class UlyssesAttention(torch.nn.Module):
     """Module wrapper: drop-in for an SDPA core inside a sequence-parallel
     block (activations arrive Shard(seq), leave Shard(seq))."""
 
-    def __init__(self, *, is_causal: bool = False, scale: Optional[float] = None):
+    def __init__(self, *, is_causal: bool = False, scale: Optional[float] = None,
+                 impl: str = "sdpa"):
         super().__init__()
         self.is_causal = is_causal
         self.scale = scale
+        self.impl = impl
 
     def forward(self, q: DTensor, k: DTensor, v: DTensor) -> DTensor:
-        return ulysses_sdpa(q, k, v, is_causal=self.is_causal, scale=self.scale)
+        return ulysses_sdpa(q, k, v, is_causal=self.is_causal, scale=self.scale,
+                            impl=self.impl)

@@ -16,6 +16,7 @@
 #include "attention_bwd.hip"
 #include "attention_fwd.hip"
 #include "attention_bwd2.hip"
+#include "attention_gen.hip"
 
 #include <vector>
 
@@ -655,6 +656,109 @@ std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v,
   return {dq, dk, dv};
 }
 
+// ------------------------------ general-shape flash attention --------------
+struct FaGenShape {
+  int B, Hq, Hkv, Sq, Sk, D, shift;
+};
+
+FaGenShape fa_gen_check(const at::Tensor& q, const at::Tensor& k,
+                        const at::Tensor& v, bool causal, int64_t shift) {
+  check_bf16_contig(q, "q");
+  check_bf16_contig(k, "k");
+  check_bf16_contig(v, "v");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+              "q, k, v must be [B, H, S, D]");
+  int64_t D = q.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "fa_gen supports head_dim 64 and 128");
+  TORCH_CHECK(k.size(3) == D && v.sizes() == k.sizes(),
+              "k, v must be [B, Hkv, Sk, D] with q's D");
+  TORCH_CHECK(k.size(0) == q.size(0), "batch dims of q and k/v differ");
+  TORCH_CHECK(k.size(1) >= 1 && q.size(1) % k.size(1) == 0,
+              "Hq must be a multiple of Hkv");
+  TORCH_CHECK(q.size(2) >= 1 && k.size(2) >= 1, "Sq and Sk must be >= 1");
+  TORCH_CHECK(q.size(0) >= 1 && q.size(0) <= 65535 && q.size(1) <= 65535,
+              "B and Hq must be in [1, 65535]");
+  TORCH_CHECK(q.size(2) + k.size(2) < (int64_t)1 << 30, "sequence too long");
+  TORCH_CHECK(causal || shift == 0, "shift needs causal");
+  // clamping to [-Sq, Sk] leaves the mask j <= i + shift unchanged
+  int64_t sh = std::max<int64_t>(-q.size(2), std::min<int64_t>(k.size(2), shift));
+  return {(int)q.size(0), (int)q.size(1), (int)k.size(1), (int)q.size(2),
+          (int)k.size(2), (int)D, (int)sh};
+}
+
+std::vector<at::Tensor> fa_gen_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                   double scale, bool causal, int64_t shift) {
+  // q: [B,Hq,Sq,D]; k,v: [B,Hkv,Sk,D] -> {o [B,Hq,Sq,D], lse [B,Hq,Sq] f32}
+  FaGenShape s = fa_gen_check(q, k, v, causal, shift);
+  auto out = at::empty_like(q);
+  auto lse = at::empty({s.B, s.Hq, s.Sq}, q.options().dtype(at::kFloat));
+  dim3 grid((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B);
+  auto kern = s.D == 64 ? fa_gen_fwd_kernel<64> : fa_gen_fwd_kernel<128>;
+  hipLaunchKernelGGL(kern, grid, dim3(FG_THREADS), 0, cur_stream(),
+                     (const unsigned short*)q.data_ptr(),
+                     (const unsigned short*)k.data_ptr(),
+                     (const unsigned short*)v.data_ptr(),
+                     (unsigned short*)out.data_ptr(), lse.data_ptr<float>(),
+                     s.Hq, s.Hkv, s.Sq, s.Sk, (float)(scale * 1.4426950408889634),
+                     causal ? 1 : 0, s.shift);
+  return {out, lse};
+}
+
+std::vector<at::Tensor> fa_gen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                   at::Tensor o, at::Tensor dout, at::Tensor lse,
+                                   c10::optional<at::Tensor> dlse, double scale,
+                                   bool causal, int64_t shift) {
+  FaGenShape s = fa_gen_check(q, k, v, causal, shift);
+  check_bf16_contig(o, "o");
+  check_bf16_contig(dout, "dout");
+  TORCH_CHECK(o.sizes() == q.sizes() && dout.sizes() == q.sizes(),
+              "o and dout must have q's shape");
+  auto check_row = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                    t.dim() == 3 && t.size(0) == s.B && t.size(1) == s.Hq &&
+                    t.size(2) == s.Sq,
+                name, " must be contiguous fp32 [B, Hq, Sq] on device");
+  };
+  check_row(lse, "lse");
+  const float* dlse_p = nullptr;
+  if (dlse.has_value()) {
+    check_row(*dlse, "dlse");
+    dlse_p = dlse->data_ptr<float>();
+  }
+  auto delta = at::empty({s.B, s.Hq, s.Sq}, q.options().dtype(at::kFloat));
+  auto dq = at::empty_like(q);
+  auto dk = at::empty_like(k);
+  auto dv = at::empty_like(v);
+  int64_t rows = (int64_t)s.B * s.Hq * s.Sq;
+  auto pre = s.D == 64 ? fa_gen_preprocess_kernel<64> : fa_gen_preprocess_kernel<128>;
+  hipLaunchKernelGGL(pre, dim3(grid_for(rows, 256 / (s.D / 8), 4096)), dim3(256),
+                     0, cur_stream(), (const unsigned short*)dout.data_ptr(),
+                     (const unsigned short*)o.data_ptr(), lse.data_ptr<float>(),
+                     dlse_p, delta.data_ptr<float>(), rows);
+  auto kkv = s.D == 64 ? fa_gen_dkdv_kernel<64> : fa_gen_dkdv_kernel<128>;
+  dim3 gridkv((s.Sk + FG_BLK - 1) / FG_BLK, s.Hkv, s.B);
+  hipLaunchKernelGGL(kkv, gridkv, dim3(FG_THREADS), 0, cur_stream(),
+                     (const unsigned short*)q.data_ptr(),
+                     (const unsigned short*)k.data_ptr(),
+                     (const unsigned short*)v.data_ptr(),
+                     (const unsigned short*)dout.data_ptr(),
+                     lse.data_ptr<float>(), delta.data_ptr<float>(),
+                     (unsigned short*)dk.data_ptr(),
+                     (unsigned short*)dv.data_ptr(), s.Hq, s.Hkv, s.Sq, s.Sk,
+                     (float)scale, causal ? 1 : 0, s.shift);
+  auto kq = s.D == 64 ? fa_gen_dq_kernel<64> : fa_gen_dq_kernel<128>;
+  dim3 gridq((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B);
+  hipLaunchKernelGGL(kq, gridq, dim3(FG_THREADS), 0, cur_stream(),
+                     (const unsigned short*)q.data_ptr(),
+                     (const unsigned short*)k.data_ptr(),
+                     (const unsigned short*)v.data_ptr(),
+                     (const unsigned short*)dout.data_ptr(),
+                     lse.data_ptr<float>(), delta.data_ptr<float>(),
+                     (unsigned short*)dq.data_ptr(), s.Hq, s.Hkv, s.Sq, s.Sk,
+                     (float)scale, causal ? 1 : 0, s.shift);
+  return {dq, dk, dv};
+}
+
 // ------------------------------ philox random ------------------------------
 ShardDesc make_desc(const std::vector<int64_t>& gshape,
                     const std::vector<int64_t>& lshape,
@@ -764,6 +868,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_bwd2", &fa_bwd2);
   m.def("fa_fwd", &fa_fwd);
   m.def("fa_fwd_ablate", &fa_fwd_ablate);
+  m.def("fa_gen_fwd", &fa_gen_fwd, pybind11::arg("q"), pybind11::arg("k"),
+        pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("causal"),
+        pybind11::arg("shift"));
+  m.def("fa_gen_bwd", &fa_gen_bwd, pybind11::arg("q"), pybind11::arg("k"),
+        pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("dout"),
+        pybind11::arg("lse"), pybind11::arg("dlse"), pybind11::arg("scale"),
+        pybind11::arg("causal"), pybind11::arg("shift"));
   m.def("permlane_probe", &permlane_probe);
   m.def("mfma32_probe", &mfma32_probe);
   m.def("tr_probe", &tr_probe);

@@ -418,6 +418,108 @@ def flash_attention_causal(q, k, v):
 
 
 # ---------------------------------------------------------------------------
+# General-shape flash attention with a differentiable LSE
+# (ops/csrc/attention_gen.hip): any Sq/Sk, D in {64,128}, MHA/GQA/MQA,
+# optional causal mask  j <= i + causal_shift.
+# ---------------------------------------------------------------------------
+def _attention_ref(q, k, v, is_causal, shift, scale, dtype=None):
+    """Differentiable torch attention returning (out, lse): the CPU path and
+    the oracle of the general kernel.  Matmuls and softmax run in `dtype`
+    (default: fp32, or q's dtype if wider); GQA by head grouping; key j is
+    visible to query i iff j <= i + shift; a row with no visible key gives
+    out = 0, lse = -inf and zero gradients."""
+    if dtype is None:
+        dtype = torch.promote_types(q.dtype, torch.float32)
+    B, Hq, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    qg = q.to(dtype).reshape(B, Hkv, Hq // Hkv, Sq, D)
+    s = (qg @ k.to(dtype).unsqueeze(2).transpose(-1, -2)) * scale
+    if is_causal:
+        i = torch.arange(Sq, device=q.device).unsqueeze(1)
+        j = torch.arange(Sk, device=q.device).unsqueeze(0)
+        s = s.masked_fill(j > i + shift, float("-inf"))
+    m = s.detach().amax(-1, keepdim=True)
+    m = torch.where(m == float("-inf"), torch.zeros_like(m), m)
+    e = torch.exp(s - m)
+    l = e.sum(-1, keepdim=True)
+    dead = l == 0
+    l1 = torch.where(dead, torch.ones_like(l), l)
+    out = (e / l1) @ v.to(dtype).unsqueeze(2)
+    lse = torch.where(dead, torch.full_like(l, float("-inf")), m + torch.log(l1))
+    lse_dtype = torch.promote_types(q.dtype, torch.float32)
+    return (out.reshape(B, Hq, Sq, D).to(q.dtype),
+            lse.reshape(B, Hq, Sq).to(lse_dtype))
+
+
+class _FlashAttentionGen(torch.autograd.Function):
+    """fa_gen_fwd / fa_gen_bwd: one node with two differentiable outputs."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, causal, shift):
+        out, lse = _ext().fa_gen_fwd(q, k, v, scale, causal, shift)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.args = (scale, causal, shift)
+        ctx.set_materialize_grads(False)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, dlse):
+        q, k, v, out, lse = ctx.saved_tensors
+        scale, causal, shift = ctx.args
+        dout = torch.zeros_like(out) if dout is None else dout.contiguous()
+        if dlse is not None:
+            dlse = dlse.float().contiguous()
+        dq, dk, dv = _ext().fa_gen_bwd(
+            q, k, v, out, dout, lse, dlse, scale, causal, shift
+        )
+        return dq, dk, dv, None, None, None
+
+
+def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
+                    return_lse=False):
+    """Attention over q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (Hq % Hkv == 0).
+
+    With is_causal, key j is visible to query i iff j <= i + causal_shift
+    (0: top-left triangle; Sk - Sq: bottom-right alignment).  A query row
+    with no visible key yields out = 0, lse = -inf and zero gradients.
+    Returns out, or (out, lse) with lse [B,Hq,Sq] fp32 (natural log) when
+    return_lse; both outputs are differentiable.
+
+    Dispatch: (1) the tuned D=128 causal kernels when their gate holds and
+    no lse is wanted; (2) the general HIP kernel for bf16 on GPU with D in
+    {64, 128}; (3) the torch reference (CPU, other dtypes / head dims,
+    VESCALE_FA=aten)."""
+    import math
+
+    if causal_shift != 0 and not is_causal:
+        raise ValueError("causal_shift != 0 requires is_causal=True")
+    B, Hq, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    hip = (
+        os.environ.get("VESCALE_FA", "hip") == "hip"
+        and all(t.is_cuda and t.dtype == torch.bfloat16 for t in (q, k, v))
+        and D in (64, 128)
+        and Hq % Hkv == 0
+        and _use_hip(q, k, v)
+    )
+    if (hip and not return_lse and is_causal and causal_shift == 0
+            and Sq == Sk and D == 128 and Sq % 256 == 0):
+        return _FlashAttention.apply(
+            q.contiguous(), k.contiguous(), v.contiguous(), scale
+        )
+    if hip:
+        out, lse = _FlashAttentionGen.apply(
+            q.contiguous(), k.contiguous(), v.contiguous(), float(scale),
+            bool(is_causal), int(causal_shift),
+        )
+    else:
+        out, lse = _attention_ref(q, k, v, is_causal, causal_shift, scale)
+    return (out, lse) if return_lse else out
+
+
+# ---------------------------------------------------------------------------
 # flat AdamW + grad utilities (no autograd)
 # ---------------------------------------------------------------------------
 @torch.no_grad()
