@@ -550,3 +550,172 @@ def test_linear_gemm8_autograd_parity():
     assert torch.allclose(y.float(), yr.float(), atol=0.05, rtol=0.05)
     assert torch.allclose(x.grad.float(), xr.grad.float(), atol=0.05, rtol=0.05)
     assert torch.allclose(w.grad.float(), wr.grad.float(), atol=0.05, rtol=0.05)
+
+
+@requires_gpu
+def test_bindings_reject_then_work():
+    """A malformed argument is a RuntimeError naming it, not a launch, and the
+    binding works right after.  Every malformed call is built so that its
+    kernel would stay inside the allocations even if the check were missing
+    (wider dtype, more elements, strided view of a larger buffer): this test
+    cannot fault the card.  Valid results are held to the fp32 references and
+    tolerances of the neighbouring per-op tests."""
+    import math
+
+    import torch.nn.functional as F
+
+    from vescale_amd.ops import build_rope_table
+    from vescale_amd.ops.functional import _rope_ref
+
+    C = _ext()
+    torch.manual_seed(40)
+    bf = dict(device="cuda", dtype=torch.bfloat16)
+    f32 = dict(device="cuda", dtype=torch.float32)
+
+    def rejects(arg, fn, *args):
+        with pytest.raises(RuntimeError, match=f"argument '{arg}'"):
+            fn(*args)
+
+    def strided(t):
+        """t's values and shape as every other column of a buffer twice as wide."""
+        big = torch.zeros(*t.shape[:-1], 2 * t.shape[-1], dtype=t.dtype, device=t.device)
+        view = big[..., ::2]
+        view.copy_(t)
+        assert not view.is_contiguous()
+        return view
+
+    # swiglu_bwd (test_swiglu: 3e-2)
+    dy, g, u = (torch.randn(4, 64, **bf) for _ in range(3))
+    rejects("dy", C.swiglu_bwd, dy.float(), g, u)
+    rejects("up", C.swiglu_bwd, dy, g, torch.cat([u, u]))
+    rejects("gate", C.swiglu_bwd, dy, strided(g), u)
+    dg, du = C.swiglu_bwd(dy, g, u)
+    gf, uf = g.float().requires_grad_(), u.float().requires_grad_()
+    (F.silu(gf) * uf).backward(dy.float())
+    assert torch.allclose(dg.float(), gf.grad, atol=3e-2, rtol=3e-2)
+    assert torch.allclose(du.float(), uf.grad, atol=3e-2, rtol=3e-2)
+
+    # ce_bwd (test_fused_cross_entropy: atol 1e-3, rtol 5e-2)
+    N, V = 4, 64
+    logits = torch.randn(N, V, **bf)
+    tgt = torch.randint(0, V, (N,), device="cuda")
+    _, lse = C.ce_fwd(logits, tgt, -100)
+    dloss = torch.full((N,), 1.0 / N, **f32)
+    rejects("lse", C.ce_bwd, logits, tgt, lse.double(), dloss, -100, False)
+    rejects("dloss", C.ce_bwd, logits, tgt, lse, torch.cat([dloss, dloss]), -100, False)
+    rejects("logits", C.ce_bwd, strided(logits), tgt, lse, dloss, -100, False)
+    dlogits = C.ce_bwd(logits, tgt, lse, dloss, -100, False)
+    lf = logits.float().requires_grad_()
+    F.cross_entropy(lf, tgt).backward()
+    assert torch.allclose(dlogits.float(), lf.grad, atol=1e-3, rtol=5e-2)
+
+    # adamw_step (test_adamw_flat: master 1e-5/1e-4, m 1e-6, v 1e-7)
+    n = 64
+    p = torch.randn(n, **bf)
+    master, grad = p.float(), torch.randn(n, **bf)
+    m, v = torch.zeros(n, **f32), torch.zeros(n, **f32)
+    hyper = (1e-3, 0.9, 0.95, 1e-8, 0.1, 1, 1.0, None)
+    pr = master.clone()
+    rejects("m", C.adamw_step, p, master, grad, m.double(), v, *hyper)
+    rejects("v", C.adamw_step, p, master, grad, m, torch.cat([v, v]), *hyper)
+    rejects("grad", C.adamw_step, p, master, strided(grad), m, v, *hyper)
+    assert torch.equal(master, pr) and not m.any() and not v.any()
+    C.adamw_step(p, master, grad, m, v, *hyper)
+    gf = grad.float()
+    pr.mul_(1 - 1e-3 * 0.1)
+    mr, vr = 0.1 * gf, 0.05 * gf * gf
+    pr.addcdiv_(mr, (vr / (1 - 0.95)).sqrt().add_(1e-8), value=-1e-3 / (1 - 0.9))
+    assert torch.allclose(master, pr, atol=1e-5, rtol=1e-4)
+    assert torch.allclose(m, mr, atol=1e-6) and torch.allclose(v, vr, atol=1e-7)
+
+    # rope_qkv_bwd (test_rope: 2e-2)
+    B, S, Hq, Hkv, D = 1, 4, 2, 1, 8
+    tab = build_rope_table(S, D, 500000.0, device="cuda")
+    dq, dk, dv = torch.randn(B, Hq, S, D, **bf), torch.randn(B, Hkv, S, D, **bf), torch.randn(B, Hkv, S, D, **bf)
+    dims = (B, S, Hq, Hkv, D, 0)
+    rejects("dq", C.rope_qkv_bwd, dq.float(), dk, dv, tab, *dims)
+    rejects("dk", C.rope_qkv_bwd, dq, torch.cat([dk, dk], 1), dv, tab, *dims)
+    rejects("dv", C.rope_qkv_bwd, dq, dk, strided(dv), tab, *dims)
+    dqkv = C.rope_qkv_bwd(dq, dk, dv, tab, *dims)
+    ref = torch.cat([
+        _rope_ref(dq.float().permute(0, 2, 1, 3), tab, 0, True).reshape(B, S, Hq * D),
+        _rope_ref(dk.float().permute(0, 2, 1, 3), tab, 0, True).reshape(B, S, Hkv * D),
+        dv.float().permute(0, 2, 1, 3).reshape(B, S, Hkv * D)], dim=-1)
+    assert dqkv.shape == ref.shape
+    assert torch.allclose(dqkv.float(), ref, atol=2e-2, rtol=2e-2)
+
+    # fa_bwd2 (test_flash_attention_bwd_kernel: dq 6e-2/8e-2, dk dv 8e-2/1e-1)
+    B, Hq, Hkv, S, D = 1, 2, 1, 256, 128
+    q = torch.randn(B, Hq, S, D, **bf, requires_grad=True)
+    k = torch.randn(B, Hkv, S, D, **bf, requires_grad=True)
+    vv = torch.randn(B, Hkv, S, D, **bf, requires_grad=True)
+    dout = torch.randn(B, Hq, S, D, **bf)
+    sc = 1.0 / math.sqrt(D)
+    qd, kd, vd = q.detach(), k.detach(), vv.detach()
+    o, lse = C.fa_fwd(qd, kd, vd, sc)
+    rejects("dout", C.fa_bwd2, qd, kd, vd, o, dout.float(), lse, sc, False)
+    rejects("lse", C.fa_bwd2, qd, kd, vd, o, dout, torch.cat([lse, lse], 2), sc, False)
+    rejects("o", C.fa_bwd2, qd, kd, vd, strided(o), dout, lse, sc, False)
+    gq, gk, gv = C.fa_bwd2(qd, kd, vd, o, dout, lse, sc, False)
+    F.scaled_dot_product_attention(q, k, vv, is_causal=True, enable_gqa=True).backward(dout)
+    assert torch.allclose(gq.float(), q.grad.float(), atol=6e-2, rtol=8e-2)
+    assert torch.allclose(gk.float(), k.grad.float(), atol=8e-2, rtol=1e-1)
+    assert torch.allclose(gv.float(), vv.grad.float(), atol=8e-2, rtol=1e-1)
+
+    # philox_uniform_ (test_philox_shard_parity: bitwise vs the flat fill)
+    desc = ([4, 4], [4, 4], [0, 0], 0, False, 1234, 7, 0.0, 1.0)
+    out = torch.full((4, 4), -1.0, **bf)
+    rejects("out", C.philox_uniform_, out.double(), *desc)
+    rejects("out", C.philox_uniform_, strided(out), *desc)
+    with pytest.raises(RuntimeError, match="prod\\(lshape\\)"):
+        C.philox_uniform_(torch.cat([out, out]), *desc)
+    assert bool((out == -1.0).all())
+    C.philox_uniform_(out, *desc)
+    flat = torch.empty(16, **bf)
+    C.philox_uniform_(flat, [16], [16], [0], 0, True, 1234, 7, 0.0, 1.0)
+    assert torch.equal(out.view(-1), flat)
+    assert bool((out.float() >= 0).all()) and bool((out.float() <= 1).all())
+    torch.cuda.synchronize()
+
+
+@requires_gpu
+def test_empty_inputs_do_not_launch():
+    """Zero rows / zero elements: correctly shaped empty (or zero) results and
+    no launch at all — a zero-size grid is a launch error that only some
+    later, unrelated call would report."""
+    from vescale_amd.ops import (
+        fused_add_rmsnorm, fused_cross_entropy, l2norm_sq, rmsnorm, scale_flat_,
+    )
+
+    bf = dict(device="cuda", dtype=torch.bfloat16)
+    x = torch.empty(0, 64, **bf, requires_grad=True)
+    r = torch.empty(0, 64, **bf, requires_grad=True)
+    w = torch.randn(64, **bf, requires_grad=True)
+
+    y = rmsnorm(x, w, 1e-5)
+    assert y.shape == (0, 64)
+    y.sum().backward()
+    assert x.grad.shape == (0, 64) and w.grad.shape == (64,) and not w.grad.any()
+
+    x.grad = w.grad = None
+    y, res = fused_add_rmsnorm(x, r, w, 1e-5)
+    assert y.shape == (0, 64) and res.shape == (0, 64)
+    (y.sum() + res.sum()).backward()
+    assert x.grad.shape == (0, 64) and r.grad.shape == (0, 64)
+    assert w.grad.shape == (64,) and not w.grad.any()
+
+    logits = torch.empty(0, 64, **bf, requires_grad=True)
+    loss = fused_cross_entropy(logits, torch.empty(0, dtype=torch.int64, device="cuda"))
+    assert loss.shape == () and float(loss) == 0.0
+    loss.backward()
+    assert logits.grad.shape == (0, 64)
+
+    for dtype in (torch.bfloat16, torch.float32):
+        e = torch.empty(0, device="cuda", dtype=dtype)
+        s = l2norm_sq(e)
+        assert s.shape == () and s.dtype == torch.float32 and float(s) == 0.0
+        scale_flat_(e, 0.5)
+        scale_flat_(e, torch.tensor(0.5, device="cuda"))
+
+    torch.cuda.synchronize()
+    assert float(torch.ones(1, device="cuda") + 1) == 2.0

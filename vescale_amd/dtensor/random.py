@@ -26,6 +26,17 @@ from .device_mesh import DeviceMesh
 from .placement_types import Replicate, Shard
 
 
+def _philox_fill_(fill, x: torch.Tensor, *args) -> torch.Tensor:
+    """In-place philox fill of x.  The bindings take contiguous tensors only
+    and never copy, so a strided x is filled through a dense buffer (the
+    row-major element order, hence every value, is the same either way)."""
+    buf = x if x.is_contiguous() else torch.empty_like(x, memory_format=torch.contiguous_format)
+    fill(buf, *args)
+    if buf is not x:
+        x.copy_(buf)
+    return x
+
+
 class _RNGStateTracker:
     def __init__(self, device_type: str = "cuda"):
         self.device_type = device_type
@@ -171,17 +182,15 @@ class ThreadBasedRNGTracker(OffsetBasedRNGTracker):
             hi = float(local_args[2]) if len(local_args) > 2 else 1.0
             if x.dtype not in (_t.bfloat16, _t.float32):
                 return NotImplemented
-            _C.philox_uniform_(x, gshape, lshape, offs, foff, flat, seed, philox_off, lo, hi)
-            return x
+            return _philox_fill_(_C.philox_uniform_, x, gshape, lshape, offs, foff, flat, seed, philox_off, lo, hi)
         if pkt == aten.normal_:
             mean = float(local_args[1]) if len(local_args) > 1 else 0.0
             std = float(local_args[2]) if len(local_args) > 2 else 1.0
             if x.dtype not in (_t.bfloat16, _t.float32):
                 return NotImplemented
-            _C.philox_normal_(x, gshape, lshape, offs, foff, flat, seed, philox_off, mean, std)
-            return x
+            return _philox_fill_(_C.philox_normal_, x, gshape, lshape, offs, foff, flat, seed, philox_off, mean, std)
         if pkt in (aten.rand_like, aten.randn_like):
-            out = _t.empty_like(x)
+            out = _t.empty_like(x, memory_format=_t.contiguous_format)
             if out.dtype not in (_t.bfloat16, _t.float32):
                 return NotImplemented
             if pkt == aten.rand_like:

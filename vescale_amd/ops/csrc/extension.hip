@@ -1,8 +1,14 @@
 // vescale_amd C++/HIP extension — single TU: kernels + torch bindings.
 //
 // Built in-tree for gfx950 only (no multi-backend dispatch, no CUDA shims).
+//
+// Every binding reads: Binding b(..) (device guard), scalar rules, b.arg(..)
+// for EACH tensor, allocate, return early when there is no work, b.launch(..).
+// Bindings never copy: callers pass contiguous tensors.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <c10/cuda/CUDAException.h>
+#include <c10/cuda/CUDAGuard.h>
 
 #include "rmsnorm.hip"
 #include "rope.hip"
@@ -18,826 +24,705 @@
 #include "attention_bwd2.hip"
 #include "attention_gen.hip"
 
+#include <climits>
+#include <sstream>
 #include <vector>
 
 namespace {
 
-inline hipStream_t cur_stream() {
-  return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
+// ------------------------------ host helpers ------------------------------
+constexpr auto BF16 = at::kBFloat16;
+constexpr auto F32 = at::kFloat;
+constexpr auto I64 = at::kLong;
+using OptTensor = c10::optional<at::Tensor>;
+
+// typed pointers (bf16 travels as unsigned short); an absent optional is null
+inline const unsigned short* bf16(const at::Tensor& t) {
+  return reinterpret_cast<const unsigned short*>(t.const_data_ptr());
+}
+inline unsigned short* bf16_mut(const at::Tensor& t) {
+  return reinterpret_cast<unsigned short*>(t.data_ptr());
+}
+inline const unsigned short* bf16(const OptTensor& t) {
+  return t.has_value() ? bf16(*t) : nullptr;
+}
+inline float* f32(const OptTensor& t) {
+  return t.has_value() ? t->data_ptr<float>() : nullptr;
 }
 
-inline void check_bf16_contig(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
-  TORCH_CHECK(t.is_cuda(), name, " must be on device");
-}
+// One or two accepted dtypes of an argument.
+struct Dtypes {
+  at::ScalarType a, b;
+  Dtypes(at::ScalarType a) : a(a), b(a) {}
+  Dtypes(at::ScalarType a, at::ScalarType b) : a(a), b(b) {}
+};
+
+// Expected sizes of an argument (-1: any extent), only its numel, or nothing.
+struct Shape {
+  at::DimVector sizes;
+  int64_t numel = -1;
+  bool any = true;
+  Shape() {}
+  Shape(at::IntArrayRef s) : sizes(s.begin(), s.end()), any(false) {}
+  Shape(std::initializer_list<int64_t> s) : sizes(s), any(false) {}
+  static Shape of_numel(int64_t n) { Shape s; s.numel = n; return s; }
+  bool matches(const at::Tensor& t) const {
+    if (any) return numel < 0 || t.numel() == numel;
+    if (t.dim() != (int64_t)sizes.size()) return false;
+    for (int64_t i = 0; i < t.dim(); ++i)
+      if (sizes[i] >= 0 && t.size(i) != sizes[i]) return false;
+    return true;
+  }
+};
+
+// Per-call context: the binding's name, the device of its first tensor and a
+// guard on that device, so allocations and the current stream belong to it.
+// arg() holds every tensor to that device and launch() holds that device to
+// be a GPU, so a call made of CPU tensors still reports a malformed argument
+// first and never reaches a kernel.
+class Binding {
+ public:
+  Binding(const char* fn, const char* first_name, const at::Tensor& first)
+      : fn(fn), first_name_(first_name), dev_(first.device()) {
+    if (first.is_cuda()) guard_.set_device(dev_);
+  }
+
+  // The one argument check: device, dtype, contiguity and shape; the
+  // message states every fact at once.
+  void arg(const char* name, const at::Tensor& t, Dtypes dt, const Shape& shape = {}) const {
+    if (t.device() == dev_ && t.is_contiguous() &&
+        (t.scalar_type() == dt.a || t.scalar_type() == dt.b) && shape.matches(t))
+      return;
+    std::ostringstream want;
+    want << "device=" << dev_ << (dev_.is_cuda() ? "" : " (must be a GPU)")
+         << " dtype=" << c10::toString(dt.a);
+    if (dt.b != dt.a) want << "|" << c10::toString(dt.b);
+    if (!shape.any) want << " sizes=" << at::IntArrayRef(shape.sizes);
+    if (shape.numel >= 0) want << " numel=" << shape.numel;
+    TORCH_CHECK(false, fn, ": argument '", name, "' expected ", want.str(),
+                " contiguous=true; got device=", t.device(), " dtype=",
+                c10::toString(t.scalar_type()), " sizes=", t.sizes(), " numel=",
+                t.numel(), " contiguous=", t.is_contiguous() ? "true" : "false");
+  }
+  void arg(const char* name, const OptTensor& t, Dtypes dt, const Shape& shape = {}) const {
+    if (t.has_value()) arg(name, *t, dt, shape);
+  }
+
+  // Last dimension of a [..., n] argument; n must be a positive multiple of mult.
+  int64_t last_dim(const char* what, const at::Tensor& t, int mult) const {
+    int64_t n = t.dim() >= 1 ? t.size(-1) : 0;
+    TORCH_CHECK(n > 0 && n % mult == 0, fn, ": ", what, " = ", n,
+                " must be a positive multiple of ", mult);
+    return n;
+  }
+
+  // The rope table must cover positions [pos_offset, pos_offset + S).
+  void rope_span(const at::Tensor& table, int64_t pos_offset, int64_t S, int64_t D) const {
+    TORCH_CHECK(D > 0 && D % 2 == 0, fn, ": head dim D = ", D, " must be even");
+    TORCH_CHECK(pos_offset >= 0, fn, ": pos_offset = ", pos_offset, " must be >= 0");
+    TORCH_CHECK(table.dim() == 3 && pos_offset + S <= table.size(0), fn,
+                ": pos_offset + S = ", pos_offset + S, " is past the table, sizes=",
+                table.sizes());
+  }
+
+  // The only launch site: on the current stream, never a zero-size grid,
+  // launch error checked.  Host-only (no sync, no allocation, no device
+  // query), so it is safe under graph capture.
+  template <typename... KArgs, typename... Args>
+  void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, Args&&... args) const {
+    TORCH_CHECK(dev_.is_cuda(), fn, ": argument '", first_name_,
+                "' expected device=a GPU; got device=", dev_);
+    TORCH_CHECK(grid.x > 0 && grid.y > 0 && grid.z > 0, fn, ": zero grid dimension (",
+                grid.x, ",", grid.y, ",", grid.z, "); return before launching when there is no work");
+    hipLaunchKernelGGL(kernel, grid, block, 0,
+                       (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
+                       std::forward<Args>(args)...);
+    C10_CUDA_KERNEL_LAUNCH_CHECK();
+  }
+
+  const char* const fn;
+
+ private:
+  const char* first_name_;
+  c10::Device dev_;
+  at::cuda::OptionalCUDAGuard guard_;
+};
+
+}  // namespace
+
+#include "probes.hip"
+
+namespace {
 
 // ------------------------------ RMSNorm ------------------------------
 std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
-  check_bf16_contig(x, "x");
-  check_bf16_contig(w, "w");
-  int hidden = (int)x.size(-1);
-  TORCH_CHECK(hidden % 8 == 0, "hidden must be a multiple of 8");
+  Binding b("rmsnorm_fwd", "x", x);
+  int hidden = (int)b.last_dim("hidden (x.size(-1))", x, 8);
+  b.arg("x", x, BF16);
+  b.arg("w", w, BF16, {hidden});
   int64_t rows = x.numel() / hidden;
   auto out = at::empty_like(x);
-  auto rrms = at::empty({rows}, x.options().dtype(at::kFloat));
-  int grid = (int)std::min<int64_t>(rows, 2048);
-  hipLaunchKernelGGL(rmsnorm_fwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const unsigned short*)x.data_ptr(),
-                     (const unsigned short*)w.data_ptr(),
-                     (unsigned short*)out.data_ptr(), rrms.data_ptr<float>(),
-                     rows, hidden, (float)eps);
+  auto rrms = at::empty({rows}, x.options().dtype(F32));
+  if (rows == 0) return {out, rrms};
+  b.launch(rmsnorm_fwd_bf16, (int)std::min<int64_t>(rows, 2048), 256, bf16(x), bf16(w),
+           bf16_mut(out), rrms.data_ptr<float>(), rows, hidden, (float)eps);
   return {out, rrms};
 }
 
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
-                                    at::Tensor rrms,
-                                    c10::optional<at::Tensor> dres) {
-  check_bf16_contig(dy, "dy");
-  check_bf16_contig(x, "x");
-  int hidden = (int)x.size(-1);
-  TORCH_CHECK(hidden <= 8192, "rmsnorm_bwd supports hidden <= 8192");
-  int64_t rows = x.numel() / hidden;
+                                    at::Tensor rrms, OptTensor dres) {
+  Binding b("rmsnorm_bwd", "dy", dy);
+  int hidden = (int)b.last_dim("hidden (dy.size(-1))", dy, 8);
+  TORCH_CHECK(hidden <= 8192, "rmsnorm_bwd supports hidden <= 8192, got ", hidden);
+  int64_t rows = dy.numel() / hidden;
+  b.arg("dy", dy, BF16);
+  b.arg("x", x, BF16, dy.sizes());
+  b.arg("w", w, BF16, {hidden});
+  b.arg("rrms", rrms, F32, {rows});
+  b.arg("dres", dres, BF16, dy.sizes());
   auto dx = at::empty_like(x);
-  TORCH_CHECK(hidden % 8 == 0, "hidden must be a multiple of 8");
-  if (rows == 0) return {dx, at::zeros({hidden}, x.options().dtype(at::kFloat))};
+  if (rows == 0) return {dx, at::zeros({hidden}, x.options().dtype(F32))};
   int grid = (int)std::min<int64_t>(rows, 1024);
   // one dw row per block, summed below in a fixed order (deterministic)
-  auto dw_part = at::empty({grid, hidden}, x.options().dtype(at::kFloat));
-  const unsigned short* dres_p = nullptr;
-  at::Tensor dres_c;
-  if (dres.has_value()) {
-    dres_c = dres->contiguous();
-    dres_p = (const unsigned short*)dres_c.data_ptr();
-  }
-  hipLaunchKernelGGL(rmsnorm_bwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const unsigned short*)dy.data_ptr(),
-                     (const unsigned short*)x.data_ptr(),
-                     (const unsigned short*)w.data_ptr(),
-                     rrms.data_ptr<float>(), dres_p,
-                     (unsigned short*)dx.data_ptr(),
-                     dw_part.data_ptr<float>(), rows, hidden);
+  auto dw_part = at::empty({grid, hidden}, x.options().dtype(F32));
+  b.launch(rmsnorm_bwd_bf16, grid, 256, bf16(dy), bf16(x), bf16(w),
+           rrms.data_ptr<float>(), bf16(dres), bf16_mut(dx), dw_part.data_ptr<float>(),
+           rows, hidden);
   return {dx, dw_part.sum(0)};
 }
 
-std::vector<at::Tensor> rmsnorm_res_fwd(at::Tensor x,
-                                        c10::optional<at::Tensor> res,
-                                        at::Tensor w, double eps) {
+std::vector<at::Tensor> rmsnorm_res_fwd(at::Tensor x, OptTensor res, at::Tensor w,
+                                        double eps) {
   // fused residual add + rmsnorm: returns {norm_out, res_new, rrms}
-  check_bf16_contig(x, "x");
-  check_bf16_contig(w, "w");
-  int hidden = (int)x.size(-1);
-  TORCH_CHECK(hidden % 8 == 0, "hidden must be a multiple of 8");
+  Binding b("rmsnorm_res_fwd", "x", x);
+  int hidden = (int)b.last_dim("hidden (x.size(-1))", x, 8);
+  b.arg("x", x, BF16);
+  b.arg("res", res, BF16, x.sizes());
+  b.arg("w", w, BF16, {hidden});
   int64_t rows = x.numel() / hidden;
   auto out = at::empty_like(x);
   auto res_out = at::empty_like(x);
-  auto rrms = at::empty({rows}, x.options().dtype(at::kFloat));
-  const unsigned short* res_p = nullptr;
-  at::Tensor res_c;
-  if (res.has_value()) {
-    res_c = res->contiguous();
-    res_p = (const unsigned short*)res_c.data_ptr();
-  }
-  int grid = (int)std::min<int64_t>(rows, 2048);
-  hipLaunchKernelGGL(rmsnorm_res_fwd_bf16, dim3(grid), dim3(256), 0,
-                     cur_stream(), (const unsigned short*)x.data_ptr(), res_p,
-                     (const unsigned short*)w.data_ptr(),
-                     (unsigned short*)out.data_ptr(),
-                     (unsigned short*)res_out.data_ptr(),
-                     rrms.data_ptr<float>(), rows, hidden, (float)eps);
+  auto rrms = at::empty({rows}, x.options().dtype(F32));
+  if (rows == 0) return {out, res_out, rrms};
+  b.launch(rmsnorm_res_fwd_bf16, (int)std::min<int64_t>(rows, 2048), 256, bf16(x),
+           bf16(res), bf16(w), bf16_mut(out), bf16_mut(res_out), rrms.data_ptr<float>(),
+           rows, hidden, (float)eps);
   return {out, res_out, rrms};
 }
 
 // ------------------------------ RoPE ------------------------------
-at::Tensor rope(at::Tensor x, at::Tensor table, int64_t pos_offset,
-                bool backward, bool inplace) {
+at::Tensor rope(at::Tensor x, at::Tensor table, int64_t pos_offset, bool backward,
+                bool inplace) {
   // x: [B, S, H, D] bf16, table: [S_max, D/2, 2] f32
-  check_bf16_contig(x, "x");
-  TORCH_CHECK(table.scalar_type() == at::kFloat && table.is_contiguous());
-  TORCH_CHECK(x.dim() == 4, "rope expects [B,S,H,D]");
+  Binding b("rope", "x", x);
+  TORCH_CHECK(x.dim() == 4, "rope: x must be [B,S,H,D], got sizes=", x.sizes());
   int B = (int)x.size(0), S = (int)x.size(1), H = (int)x.size(2), D = (int)x.size(3);
-  TORCH_CHECK(D % 2 == 0);
+  b.rope_span(table, pos_offset, S, D);
+  b.arg("x", x, BF16);
+  b.arg("table", table, F32, {-1, D / 2, 2});
   auto out = inplace ? x : at::empty_like(x);
   int64_t n_tokens = (int64_t)B * S * H;
   int64_t pairs = n_tokens * (D / 2);
-  int grid = grid_for(pairs / 2, 256);
-  hipLaunchKernelGGL(rope_fwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const unsigned short*)x.data_ptr(),
-                     (unsigned short*)out.data_ptr(), table.data_ptr<float>(),
-                     n_tokens, H, S, D, (int)pos_offset, backward ? 1 : 0);
+  b.launch(rope_fwd_bf16, grid_for(pairs / 2, 256), 256, bf16(x), bf16_mut(out),
+           table.data_ptr<float>(), n_tokens, H, S, D, (int)pos_offset,
+           backward ? 1 : 0);
   return out;
 }
 
-std::vector<at::Tensor> rope_qkv_fwd(at::Tensor qkv, at::Tensor table,
-                                     int64_t B, int64_t S, int64_t Hq,
-                                     int64_t Hkv, int64_t D,
+// Scalar rules shared by rope_qkv_fwd / rope_qkv_bwd; returns the number of
+// (token, head, pair) work items.
+int64_t rope_qkv_check(const Binding& b, const at::Tensor& table, int64_t B, int64_t S,
+                       int64_t Hq, int64_t Hkv, int64_t D, int64_t pos_offset) {
+  TORCH_CHECK(B >= 0 && S >= 0 && Hq >= 0 && Hkv >= 0 && D <= INT_MAX &&
+                  S <= INT_MAX && Hq <= INT_MAX && Hkv <= INT_MAX,
+              b.fn, ": B, S, Hq, Hkv must be >= 0 and fit int");
+  b.rope_span(table, pos_offset, S, D);
+  return B * S * (Hq + 2 * Hkv) * (D / 2);
+}
+
+std::vector<at::Tensor> rope_qkv_fwd(at::Tensor qkv, at::Tensor table, int64_t B,
+                                     int64_t S, int64_t Hq, int64_t Hkv, int64_t D,
                                      int64_t pos_offset) {
-  check_bf16_contig(qkv, "qkv");
-  int64_t T = B * S;
+  Binding b("rope_qkv_fwd", "qkv", qkv);
+  int64_t total = rope_qkv_check(b, table, B, S, Hq, Hkv, D, pos_offset);
+  b.arg("qkv", qkv, BF16, Shape::of_numel(total * 2));
+  b.arg("table", table, F32, {-1, D / 2, 2});
   auto opt = qkv.options();
   auto q = at::empty({B, Hq, S, D}, opt);
   auto k = at::empty({B, Hkv, S, D}, opt);
   auto v = at::empty({B, Hkv, S, D}, opt);
-  int64_t total = T * (Hq + 2 * Hkv) * (D / 2);
-  int grid = grid_for(total, 256);
-  hipLaunchKernelGGL(rope_qkv_fwd_bf16, dim3(grid), dim3(256), 0,
-                     cur_stream(), (const unsigned short*)qkv.data_ptr(),
-                     (unsigned short*)q.data_ptr(),
-                     (unsigned short*)k.data_ptr(),
-                     (unsigned short*)v.data_ptr(), table.data_ptr<float>(),
-                     T, (int)S, (int)Hq, (int)Hkv, (int)D, (int)pos_offset);
+  b.launch(rope_qkv_fwd_bf16, grid_for(total, 256), 256, bf16(qkv), bf16_mut(q),
+           bf16_mut(k), bf16_mut(v), table.data_ptr<float>(), B * S, (int)S, (int)Hq,
+           (int)Hkv, (int)D, (int)pos_offset);
   return {q, k, v};
 }
 
-at::Tensor rope_qkv_bwd(at::Tensor dq, at::Tensor dk, at::Tensor dv,
-                        at::Tensor table, int64_t B, int64_t S, int64_t Hq,
-                        int64_t Hkv, int64_t D, int64_t pos_offset) {
-  int64_t T = B * S;
+at::Tensor rope_qkv_bwd(at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor table,
+                        int64_t B, int64_t S, int64_t Hq, int64_t Hkv, int64_t D,
+                        int64_t pos_offset) {
+  Binding b("rope_qkv_bwd", "dq", dq);
+  int64_t total = rope_qkv_check(b, table, B, S, Hq, Hkv, D, pos_offset);
+  b.arg("dq", dq, BF16, {B, Hq, S, D});
+  b.arg("dk", dk, BF16, {B, Hkv, S, D});
+  b.arg("dv", dv, BF16, {B, Hkv, S, D});
+  b.arg("table", table, F32, {-1, D / 2, 2});
   auto dqkv = at::empty({B, S, (Hq + 2 * Hkv) * D}, dq.options());
-  int64_t total = T * (Hq + 2 * Hkv) * (D / 2);
-  int grid = grid_for(total, 256);
-  hipLaunchKernelGGL(rope_qkv_bwd_bf16, dim3(grid), dim3(256), 0,
-                     cur_stream(),
-                     (const unsigned short*)dq.contiguous().data_ptr(),
-                     (const unsigned short*)dk.contiguous().data_ptr(),
-                     (const unsigned short*)dv.contiguous().data_ptr(),
-                     (unsigned short*)dqkv.data_ptr(), table.data_ptr<float>(),
-                     T, (int)S, (int)Hq, (int)Hkv, (int)D, (int)pos_offset);
+  b.launch(rope_qkv_bwd_bf16, grid_for(total, 256), 256, bf16(dq), bf16(dk), bf16(dv),
+           bf16_mut(dqkv), table.data_ptr<float>(), B * S, (int)S, (int)Hq, (int)Hkv,
+           (int)D, (int)pos_offset);
   return dqkv;
 }
 
 // ------------------------------ SwiGLU ------------------------------
 at::Tensor swiglu_fwd(at::Tensor gate, at::Tensor up) {
-  check_bf16_contig(gate, "gate");
-  check_bf16_contig(up, "up");
+  Binding b("swiglu_fwd", "gate", gate);
+  b.arg("gate", gate, BF16);
+  b.arg("up", up, BF16, gate.sizes());
   auto out = at::empty_like(gate);
   int64_t n = gate.numel();
-  int grid = grid_for(n / 8, 256);
-  hipLaunchKernelGGL(swiglu_fwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const unsigned short*)gate.data_ptr(),
-                     (const unsigned short*)up.data_ptr(),
-                     (unsigned short*)out.data_ptr(), n);
+  b.launch(swiglu_fwd_bf16, grid_for(n / 8, 256), 256, bf16(gate), bf16(up),
+           bf16_mut(out), n);
   return out;
 }
 
+std::vector<at::Tensor> swiglu_bwd(at::Tensor dy, at::Tensor gate, at::Tensor up) {
+  Binding b("swiglu_bwd", "dy", dy);
+  b.arg("dy", dy, BF16);
+  b.arg("gate", gate, BF16, dy.sizes());
+  b.arg("up", up, BF16, dy.sizes());
+  auto dgate = at::empty_like(gate);
+  auto dup = at::empty_like(up);
+  int64_t n = gate.numel();
+  b.launch(swiglu_bwd_bf16, grid_for(n / 8, 256), 256, bf16(dy), bf16(gate), bf16(up),
+           bf16_mut(dgate), bf16_mut(dup), n);
+  return {dgate, dup};
+}
+
 at::Tensor swiglu_packed_fwd(at::Tensor gu) {
-  check_bf16_contig(gu, "gu");
-  int F2 = (int)gu.size(-1);
-  TORCH_CHECK(F2 % 16 == 0, "packed ffn dim must be multiple of 16");
-  int F = F2 / 2;
-  int64_t rows = gu.numel() / F2;
+  Binding b("swiglu_packed_fwd", "gu", gu);
+  int F = (int)b.last_dim("packed ffn dim F2 (gu.size(-1))", gu, 16) / 2;
+  b.arg("gu", gu, BF16);
+  int64_t rows = gu.numel() / (2 * F);
   auto sizes = gu.sizes().vec();
   sizes.back() = F;
   auto out = at::empty(sizes, gu.options());
-  int grid = grid_for(rows * (F / 8), 256);
-  hipLaunchKernelGGL(swiglu_packed_fwd_bf16, dim3(grid), dim3(256), 0,
-                     cur_stream(), (const unsigned short*)gu.data_ptr(),
-                     (unsigned short*)out.data_ptr(), rows, F);
+  b.launch(swiglu_packed_fwd_bf16, grid_for(rows * (F / 8), 256), 256, bf16(gu),
+           bf16_mut(out), rows, F);
   return out;
 }
 
 at::Tensor swiglu_packed_bwd(at::Tensor dy, at::Tensor gu) {
-  int F2 = (int)gu.size(-1);
-  int F = F2 / 2;
-  int64_t rows = gu.numel() / F2;
+  Binding b("swiglu_packed_bwd", "dy", dy);
+  int F = (int)b.last_dim("packed ffn dim F2 (gu.size(-1))", gu, 16) / 2;
+  auto sizes = gu.sizes().vec();
+  sizes.back() = F;
+  b.arg("dy", dy, BF16, at::IntArrayRef(sizes));
+  b.arg("gu", gu, BF16);
+  int64_t rows = gu.numel() / (2 * F);
   auto dgu = at::empty_like(gu);
-  int grid = grid_for(rows * (F / 8), 256);
-  hipLaunchKernelGGL(swiglu_packed_bwd_bf16, dim3(grid), dim3(256), 0,
-                     cur_stream(), (const unsigned short*)dy.contiguous().data_ptr(),
-                     (const unsigned short*)gu.data_ptr(),
-                     (unsigned short*)dgu.data_ptr(), rows, F);
+  b.launch(swiglu_packed_bwd_bf16, grid_for(rows * (F / 8), 256), 256, bf16(dy),
+           bf16(gu), bf16_mut(dgu), rows, F);
   return dgu;
 }
 
-std::vector<at::Tensor> swiglu_bwd(at::Tensor dy, at::Tensor gate, at::Tensor up) {
-  auto dgate = at::empty_like(gate);
-  auto dup = at::empty_like(up);
-  int64_t n = gate.numel();
-  int grid = grid_for(n / 8, 256);
-  hipLaunchKernelGGL(swiglu_bwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const unsigned short*)dy.data_ptr(),
-                     (const unsigned short*)gate.data_ptr(),
-                     (const unsigned short*)up.data_ptr(),
-                     (unsigned short*)dgate.data_ptr(),
-                     (unsigned short*)dup.data_ptr(), n);
-  return {dgate, dup};
-}
-
 // ------------------------------ Cross entropy ------------------------------
+// Target VALUES are not read here (that would need a device sync): every
+// target inside [0, vocab) or equal to ignore_index is the caller's duty.
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target,
                                int64_t ignore_index) {
-  check_bf16_contig(logits, "logits");
-  TORCH_CHECK(target.scalar_type() == at::kLong && target.is_contiguous());
-  int vocab = (int)logits.size(-1);
-  TORCH_CHECK(vocab % 8 == 0, "vocab must be a multiple of 8");
+  Binding b("ce_fwd", "logits", logits);
+  int vocab = (int)b.last_dim("vocab (logits.size(-1))", logits, 8);
   int64_t rows = logits.numel() / vocab;
-  auto loss = at::empty({rows}, logits.options().dtype(at::kFloat));
-  auto lse = at::empty({rows}, logits.options().dtype(at::kFloat));
-  int grid = (int)std::min<int64_t>(rows, 2048);
-  hipLaunchKernelGGL(ce_fwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const unsigned short*)logits.data_ptr(),
-                     target.data_ptr<int64_t>(), loss.data_ptr<float>(),
-                     lse.data_ptr<float>(), rows, vocab, ignore_index);
+  b.arg("logits", logits, BF16);
+  b.arg("target", target, I64, Shape::of_numel(rows));
+  auto loss = at::empty({rows}, logits.options().dtype(F32));
+  auto lse = at::empty({rows}, logits.options().dtype(F32));
+  if (rows == 0) return {loss, lse};
+  b.launch(ce_fwd_bf16, (int)std::min<int64_t>(rows, 2048), 256, bf16(logits),
+           target.data_ptr<int64_t>(), loss.data_ptr<float>(), lse.data_ptr<float>(),
+           rows, vocab, ignore_index);
   return {loss, lse};
 }
 
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
                   at::Tensor dloss, int64_t ignore_index, bool inplace) {
-  int vocab = (int)logits.size(-1);
+  Binding b("ce_bwd", "logits", logits);
+  int vocab = (int)b.last_dim("vocab (logits.size(-1))", logits, 8);
   int64_t rows = logits.numel() / vocab;
+  b.arg("logits", logits, BF16);
+  b.arg("target", target, I64, Shape::of_numel(rows));
+  b.arg("lse", lse, F32, {rows});
+  b.arg("dloss", dloss, F32, {rows});
   auto dlogits = inplace ? logits : at::empty_like(logits);
-  int grid = (int)std::min<int64_t>(rows, 2048);
-  hipLaunchKernelGGL(ce_bwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const unsigned short*)logits.data_ptr(),
-                     (unsigned short*)dlogits.data_ptr(),
-                     target.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                     dloss.data_ptr<float>(), rows, vocab, ignore_index);
+  if (rows == 0) return dlogits;
+  b.launch(ce_bwd_bf16, (int)std::min<int64_t>(rows, 2048), 256, bf16(logits),
+           bf16_mut(dlogits), target.data_ptr<int64_t>(), lse.data_ptr<float>(),
+           dloss.data_ptr<float>(), rows, vocab, ignore_index);
   return dlogits;
 }
 
 // ------------------------------ AdamW ------------------------------
-void adamw_step(at::Tensor param, c10::optional<at::Tensor> master,
-                at::Tensor grad, at::Tensor m, at::Tensor v, double lr,
-                double beta1, double beta2, double eps, double weight_decay,
-                int64_t step, double grad_scale,
-                c10::optional<at::Tensor> clip_scale) {
-  check_bf16_contig(param, "param");
+void adamw_step(at::Tensor param, OptTensor master, at::Tensor grad, at::Tensor m,
+                at::Tensor v, double lr, double beta1, double beta2, double eps,
+                double weight_decay, int64_t step, double grad_scale,
+                OptTensor clip_scale) {
+  Binding b("adamw_step", "param", param);
+  TORCH_CHECK(step >= 1, "adamw_step: step = ", step, " must be >= 1");
   int64_t n = param.numel();
+  b.arg("param", param, BF16);
+  b.arg("master", master, F32, Shape::of_numel(n));
+  b.arg("grad", grad, {BF16, F32}, Shape::of_numel(n));
+  b.arg("m", m, F32, Shape::of_numel(n));
+  b.arg("v", v, F32, Shape::of_numel(n));
+  b.arg("clip_scale", clip_scale, F32);
+  TORCH_CHECK(!clip_scale.has_value() || clip_scale->numel() >= 1,
+              "adamw_step: argument 'clip_scale' needs at least one element");
   float bc1 = 1.f - powf((float)beta1, (float)step);
   float bc2 = 1.f - powf((float)beta2, (float)step);
-  const unsigned short* gb = nullptr;
-  const float* gf = nullptr;
-  if (grad.scalar_type() == at::kBFloat16) gb = (const unsigned short*)grad.data_ptr();
-  else gf = grad.data_ptr<float>();
-  float* mp = master.has_value() ? master->data_ptr<float>() : nullptr;
-  const float* cp = clip_scale.has_value() ? clip_scale->data_ptr<float>() : nullptr;
-  int grid = grid_for(n / 8, 256);
-  hipLaunchKernelGGL(adamw_flat_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (unsigned short*)param.data_ptr(), mp, gb, gf,
-                     m.data_ptr<float>(), v.data_ptr<float>(), n, (float)lr,
-                     (float)beta1, (float)beta2, (float)eps,
-                     (float)weight_decay, bc1, bc2, (float)grad_scale, cp);
+  bool gbf = grad.scalar_type() == BF16;
+  b.launch(adamw_flat_bf16, grid_for(n / 8, 256), 256, bf16_mut(param), f32(master),
+           gbf ? bf16(grad) : nullptr, gbf ? nullptr : grad.data_ptr<float>(),
+           m.data_ptr<float>(), v.data_ptr<float>(), n, (float)lr, (float)beta1,
+           (float)beta2, (float)eps, (float)weight_decay, bc1, bc2, (float)grad_scale,
+           f32(clip_scale));
 }
 
 at::Tensor l2norm_sq(at::Tensor x) {
+  Binding b("l2norm_sq", "x", x);
+  b.arg("x", x, {BF16, F32});
   int64_t n = x.numel();
+  if (n == 0) return at::zeros({1}, x.options().dtype(F32));
   int grid = grid_for(n / 8, 256);
-  auto part = at::empty({grid}, x.options().dtype(at::kFloat));
-  const unsigned short* xb = nullptr;
-  const float* xf = nullptr;
-  if (x.scalar_type() == at::kBFloat16) xb = (const unsigned short*)x.data_ptr();
-  else xf = x.data_ptr<float>();
-  hipLaunchKernelGGL(l2norm_sq_flat, dim3(grid), dim3(256), 0, cur_stream(),
-                     xb, xf, part.data_ptr<float>(), n);
+  auto part = at::empty({grid}, x.options().dtype(F32));
+  bool xbf = x.scalar_type() == BF16;
+  b.launch(l2norm_sq_flat, grid, 256, xbf ? bf16(x) : nullptr,
+           xbf ? nullptr : x.data_ptr<float>(), part.data_ptr<float>(), n);
   return part.sum(0, /*keepdim=*/true);
 }
 
-void scale_(at::Tensor x, c10::optional<at::Tensor> scale_t, double scale_c) {
+void scale_(at::Tensor x, OptTensor scale_t, double scale_c) {
+  Binding b("scale_", "x", x);
+  b.arg("x", x, {BF16, F32});
+  b.arg("scale_t", scale_t, F32);
+  TORCH_CHECK(!scale_t.has_value() || scale_t->numel() >= 1,
+              "scale_: argument 'scale_t' needs at least one element");
   int64_t n = x.numel();
-  unsigned short* xb = nullptr;
-  float* xf = nullptr;
-  if (x.scalar_type() == at::kBFloat16) xb = (unsigned short*)x.data_ptr();
-  else xf = x.data_ptr<float>();
-  const float* sp = scale_t.has_value() ? scale_t->data_ptr<float>() : nullptr;
-  int grid = grid_for(n / 8, 256);
-  hipLaunchKernelGGL(scale_flat, dim3(grid), dim3(256), 0, cur_stream(), xb,
-                     xf, sp, (float)scale_c, n);
+  if (n == 0) return;
+  bool xbf = x.scalar_type() == BF16;
+  b.launch(scale_flat, grid_for(n / 8, 256), 256, xbf ? bf16_mut(x) : nullptr,
+           xbf ? nullptr : x.data_ptr<float>(), f32(scale_t), (float)scale_c, n);
 }
 
 // ------------------------------ MFMA GEMM ------------------------------
+// C[M,N] = a[M,K] @ b[N,K]^T: operand checks shared by gemm_tn / gemm_tn8.
+void gemm_check(const Binding& b, const at::Tensor& a, const at::Tensor& bm, int BM,
+                int BN, int BK) {
+  TORCH_CHECK(a.dim() == 2 && bm.dim() == 2, b.fn, ": a and b must be 2-D, got a sizes=",
+              a.sizes(), " b sizes=", bm.sizes());
+  int64_t M = a.size(0), K = a.size(1), N = bm.size(0);
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && M <= INT_MAX && N <= INT_MAX && K <= INT_MAX,
+              b.fn, ": M, N, K must be >= 1 and fit int");
+  TORCH_CHECK(M % BM == 0 && N % BN == 0 && K % BK == 0, b.fn,
+              " tile divisibility violated: requires M % ", BM, " == 0, N % ", BN,
+              " == 0 and K % ", BK, " == 0");
+  b.arg("a", a, BF16);
+  b.arg("b", bm, BF16, {N, K});
+}
+
 at::Tensor gemm_tn(at::Tensor a, at::Tensor b, int64_t variant) {
-  // C[M,N] = a[M,K] @ b[N,K]^T
-  check_bf16_contig(a, "a");
-  check_bf16_contig(b, "b");
-  int64_t M = a.size(0), K = a.size(1), N = b.size(0);
-  TORCH_CHECK(b.size(1) == K, "K mismatch");
+  Binding bd("gemm_tn", "a", a);
+  TORCH_CHECK(variant >= 0 && variant <= 4, "gemm_tn: variant = ", variant,
+              " must be in 0..4");
   int BM = variant == 1 ? 128 : (variant == 3 ? 128 : (variant == 4 ? 512 : 256));
   int BN = variant == 3 ? 128 : 256;
   int BK = variant == 1 ? 64 : 32;
   int threads = variant == 3 ? 256 : (variant == 4 ? 1024 : 512);
-  TORCH_CHECK(M % BM == 0 && N % BN == 0 && K % BK == 0,
-              "gemm_tn tile divisibility violated");
+  gemm_check(bd, a, b, BM, BN, BK);
+  int64_t M = a.size(0), K = a.size(1), N = b.size(0);
   auto c = at::empty({M, N}, a.options());
-  int grid = (int)((M / BM) * (N / BN));
-  auto kern = gemm_tn_bf16_v0;
-  if (variant == 1) kern = gemm_tn_bf16_v1;
-  if (variant == 2) kern = gemm_tn_bf16_v2;
-  if (variant == 3) kern = gemm_tn_bf16_v3;
-  if (variant == 4) kern = gemm_tn_bf16_v4;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, cur_stream(),
-                     (const unsigned short*)a.data_ptr(),
-                     (const unsigned short*)b.data_ptr(),
-                     (unsigned short*)c.data_ptr(), (int)M, (int)N, (int)K);
+  decltype(&gemm_tn_bf16_v0) kerns[] = {gemm_tn_bf16_v0, gemm_tn_bf16_v1, gemm_tn_bf16_v2,
+                                        gemm_tn_bf16_v3, gemm_tn_bf16_v4};
+  bd.launch(kerns[variant], (int)((M / BM) * (N / BN)), threads, bf16(a), bf16(b),
+            bf16_mut(c), (int)M, (int)N, (int)K);
   return c;
 }
 
 at::Tensor gemm_tn8(at::Tensor a, at::Tensor b, int64_t mode) {
-  // C[M,N] = A[M,K] . B[N,K]^T via the 8-phase 256x256 template (gemm8.hip)
-  check_bf16_contig(a, "a");
-  check_bf16_contig(b, "b");
+  // via the 8-phase 256x256 template (gemm8.hip)
+  Binding bd("gemm_tn8", "a", a);
+  TORCH_CHECK(mode >= 0 && mode <= 8, "gemm_tn8: mode = ", mode, " must be in 0..8");
+  gemm_check(bd, a, b, G8_BM, G8_BN, G8_BK);
   int64_t M = a.size(0), K = a.size(1), N = b.size(0);
-  TORCH_CHECK(b.size(1) == K, "K mismatch");
-  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0,
-              "gemm_tn8 requires M,N % 256 == 0 and K % 64 == 0");
-  auto c = at::empty({M, N}, a.options());
-  dim3 grid((unsigned)(M / 256), (unsigned)(N / 256), 1);
   TORCH_CHECK(mode != 5 || (K / 64) % 2 == 0, "mode 5 needs K % 128 == 0");
   TORCH_CHECK((mode != 7 && mode != 8) || ((K / 64) % 2 == 0 && K / 64 >= 4),
               "modes 7/8 need an even K/64 >= 4");
-  auto kern = mode == 8   ? gemm8_tn_bf16_rot9
-              : mode == 7 ? gemm8_tn_bf16_rot8
-              : mode == 6 ? gemm8_tn_bf16_rot3ra
-              : mode == 5 ? gemm8_tn_bf16_rot3u2
-              : mode == 4 ? gemm8_tn_bf16_rot3np
-              : mode == 3 ? gemm8_tn_bf16_rot3
-              : mode == 2 ? gemm8_tn_bf16_rot
-              : mode == 1 ? gemm8_tn_bf16_lockstep
-                          : gemm8_tn_bf16;
-  hipLaunchKernelGGL(kern, grid, dim3(G8_THREADS), 0, cur_stream(),
-                     (const unsigned short*)a.data_ptr(),
-                     (const unsigned short*)b.data_ptr(),
-                     (unsigned short*)c.data_ptr(), (int)M, (int)N, (int)K);
+  auto c = at::empty({M, N}, a.options());
+  decltype(&gemm8_tn_bf16) kerns[] = {  // indexed by mode
+      gemm8_tn_bf16,        gemm8_tn_bf16_lockstep, gemm8_tn_bf16_rot,
+      gemm8_tn_bf16_rot3,   gemm8_tn_bf16_rot3np,   gemm8_tn_bf16_rot3u2,
+      gemm8_tn_bf16_rot3ra, gemm8_tn_bf16_rot8,     gemm8_tn_bf16_rot9};
+  bd.launch(kerns[mode], dim3((unsigned)(M / 256), (unsigned)(N / 256), 1), G8_THREADS,
+            bf16(a), bf16(b), bf16_mut(c), (int)M, (int)N, (int)K);
   return c;
 }
 
-// ------------------------------ flash-attention backward -------------------
-std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                               at::Tensor o, at::Tensor dout, at::Tensor lse,
-                               double scale) {
-  // q,o,dout: [B,Hq,S,D]; k,v: [B,Hkv,S,D]; lse: [B,Hq,S] fp32; causal
-  check_bf16_contig(q, "q");
-  check_bf16_contig(k, "k");
-  check_bf16_contig(v, "v");
-  check_bf16_contig(o, "o");
-  int B = (int)q.size(0), Hq = (int)q.size(1), S = (int)q.size(2), D = (int)q.size(3);
-  int Hkv = (int)k.size(1);
-  TORCH_CHECK(D == FA_D, "fa_bwd supports head_dim 128");
-  TORCH_CHECK(S % FA_BLK == 0, "seq must be a multiple of 64");
-  TORCH_CHECK(lse.scalar_type() == at::kFloat);
-  auto lse_c = lse.contiguous();
-  auto dout_c = dout.contiguous();
-  auto delta = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  int64_t rows = (int64_t)B * Hq * S;
-  hipLaunchKernelGGL(fa_bwd_preprocess, dim3(grid_for(rows, 1, 4096)), dim3(256),
-                     0, cur_stream(),
-                     (const unsigned short*)dout_c.data_ptr(),
-                     (const unsigned short*)o.data_ptr(),
-                     delta.data_ptr<float>(), rows);
-  auto dq = at::empty_like(q);
-  auto dk_part = at::empty({B, Hq, S, D}, q.options());
-  auto dv_part = at::empty({B, Hq, S, D}, q.options());
-  dim3 gridkv(S / FA_BLK, Hq, B);
-  hipLaunchKernelGGL(fa_bwd_dkdv, gridkv, dim3(FA_THREADS), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (const unsigned short*)dout_c.data_ptr(),
-                     lse_c.data_ptr<float>(), delta.data_ptr<float>(),
-                     (unsigned short*)dk_part.data_ptr(),
-                     (unsigned short*)dv_part.data_ptr(), B, Hq, Hkv, S,
-                     (float)scale);
-  hipLaunchKernelGGL(fa_bwd_dq, gridkv, dim3(FA_THREADS), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (const unsigned short*)dout_c.data_ptr(),
-                     lse_c.data_ptr<float>(), delta.data_ptr<float>(),
-                     (unsigned short*)dq.data_ptr(), B, Hq, Hkv, S,
-                     (float)scale);
-  at::Tensor dk, dv;
-  if (Hkv == Hq) {
-    dk = dk_part;
-    dv = dv_part;
-  } else {
-    dk = at::empty({B, Hkv, S, D}, q.options());
-    dv = at::empty({B, Hkv, S, D}, q.options());
-    int64_t SD = (int64_t)S * D;
-    int grid = grid_for((int64_t)B * Hkv * SD / 8, 256);
-    hipLaunchKernelGGL(fa_bwd_reduce_gqa, dim3(grid), dim3(256), 0,
-                       cur_stream(),
-                       (const unsigned short*)dk_part.data_ptr(),
-                       (unsigned short*)dk.data_ptr(), B, Hq, Hkv, SD);
-    hipLaunchKernelGGL(fa_bwd_reduce_gqa, dim3(grid), dim3(256), 0,
-                       cur_stream(),
-                       (const unsigned short*)dv_part.data_ptr(),
-                       (unsigned short*)dv.data_ptr(), B, Hq, Hkv, SD);
-  }
-  return {dq, dk, dv};
-}
+// ------------------------------ tuned flash attention (causal, D=128) ------
+struct FaShape { int B, Hq, Hkv, S; };
 
-// ------------------------------ flash-attention forward --------------------
-extern "C" __global__ void permlane_probe_kernel(int* out) {
-  int x = (int)threadIdx.x;
-  auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  out[threadIdx.x] = (r[0] << 16) | (r[1] & 0xFFFF);
+// q,o,dout: [B,Hq,S,128]; k,v: [B,Hkv,S,128]; lse: [B,Hq,S] f32; S % tile == 0.
+// The forward bindings pass no o/dout/lse.
+FaShape fa_check(const Binding& b, int tile, const at::Tensor& q, const at::Tensor& k,
+                 const at::Tensor& v, const OptTensor& o = {},
+                 const OptTensor& dout = {}, const OptTensor& lse = {}) {
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, b.fn, ": q, k must be [B,H,S,128], got q sizes=",
+              q.sizes(), " k sizes=", k.sizes());
+  int64_t B = q.size(0), Hq = q.size(1), S = q.size(2), Hkv = k.size(1);
+  TORCH_CHECK(S >= 1 && S % tile == 0 && S <= INT_MAX, b.fn, ": seq = ", S,
+              " must be a positive multiple of ", tile);
+  TORCH_CHECK(B >= 1 && Hkv >= 1 && Hq >= 1 && Hq % Hkv == 0, b.fn, ": B = ", B,
+              " must be >= 1 and Hq = ", Hq, " a positive multiple of Hkv = ", Hkv);
+  b.arg("q", q, BF16, {B, Hq, S, FF_D});
+  b.arg("k", k, BF16, {B, Hkv, S, FF_D});
+  b.arg("v", v, BF16, {B, Hkv, S, FF_D});
+  b.arg("o", o, BF16, {B, Hq, S, FF_D});
+  b.arg("dout", dout, BF16, {B, Hq, S, FF_D});
+  b.arg("lse", lse, F32, {B, Hq, S});
+  return {(int)B, (int)Hq, (int)Hkv, (int)S};
 }
+static_assert(FA_D == FF_D && FB_D == FF_D, "tuned attention kernels share D");
 
-// mfma_f32_32x32x16_bf16 layout probe: builds A/B frags per the ASSUMED
-// layout (operand row/col = lane&31, k = (lane>>5)*8 + e) and dumps D for
-// three tests; see tools/fa_fwd_check.py for decoding.
-extern "C" __global__ void mfma32_probe_kernel(float* out) {
-  typedef short sx8 __attribute__((ext_vector_type(8)));
-  typedef float fx16 __attribute__((ext_vector_type(16)));
-  int lane = threadIdx.x & 63;
-  int l31 = lane & 31, half = lane >> 5;
-  sx8 af, bf, a1, bj, ak, bk;
-  for (int e = 0; e < 8; ++e) {
-    int k = half * 8 + e;
-    af[e] = (short)f32_to_bf16((float)((k == 0) ? l31 : 0));
-    bf[e] = (short)f32_to_bf16((float)((k == 0) ? 1 : 0));
-    a1[e] = bf[e];
-    bj[e] = (short)f32_to_bf16((float)((k == 0) ? l31 : 0));
-    ak[e] = (short)f32_to_bf16((float)((k == 5) ? 1 : 0));
-    bk[e] = (short)f32_to_bf16((float)((k == 5) ? l31 : 0));
-  }
-  fx16 z = (fx16)(0.f);
-  fx16 d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, z, 0, 0, 0);
-  fx16 d2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bj, z, 0, 0, 0);
-  fx16 d3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, bk, z, 0, 0, 0);
-  for (int r = 0; r < 16; ++r) {
-    out[0 * 64 * 16 + lane * 16 + r] = d1[r];
-    out[1 * 64 * 16 + lane * 16 + r] = d2[r];
-    out[2 * 64 * 16 + lane * 16 + r] = d3[r];
-  }
-}
-
-at::Tensor mfma32_probe() {
-  auto out = at::empty({3, 64, 16}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA));
-  hipLaunchKernelGGL(mfma32_probe_kernel, dim3(1), dim3(64), 0, cur_stream(),
-                     out.data_ptr<float>());
-  return out;
-}
-
-// tr-read addressing probe for the 4x4-group transpose scheme: stage a
-// pattern (value = kv*128 + d) through the SAME swizzled store the kernel
-// uses, then perform the kernel's exact PV reads; host checks lane l elem
-// e == (ks*16 + half*8 + e)*128 + ds*32 + l31 (tools/tr_probe_check.py).
-extern "C" __global__ void tr_probe_kernel(unsigned short* out) {
-  __shared__ unsigned short lvp[FF_KV * FF_D];
-  int tid = threadIdx.x;
-  for (int i = tid * 8; i < FF_KV * FF_D; i += 64 * 8) {
-    ff_shortx8 vv;
-#pragma unroll
-    for (int x = 0; x < 8; ++x) vv[x] = (short)(i + x);
-    *reinterpret_cast<ff_shortx8*>((char*)lvp + ff_kswz(i * 2)) = vv;
-  }
-  __syncthreads();
-  int lane = tid & 63;
-  int l31 = lane & 31;
-  int half = lane >> 5;
-  for (int ds = 0; ds < 4; ++ds) {
-    const int col2 = (ds * 32 + (l31 & 16) + (lane & 3) * 4) * 2;
-    const int row0 = half * 8 + ((lane & 15) >> 2);
-    const int a0 = (row0 * 256 + col2) ^ ((row0 & 7) << 4);
-    const int row1 = row0 + 4;
-    const int a1 = (row1 * 256 + col2) ^ ((row1 & 7) << 4);
-    ff_lds_p b0 = (ff_lds_p)((const char*)lvp + a0);
-    ff_lds_p b1 = (ff_lds_p)((const char*)lvp + a1);
-    ff_shortx4 t0, t1;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      switch (ks) {
-        case 0: asm volatile("ds_read_b64_tr_b16 %0, %2 offset:0\n\tds_read_b64_tr_b16 %1, %3 offset:0" : "=v"(t0), "=v"(t1) : "v"(b0), "v"(b1)); break;
-        case 1: asm volatile("ds_read_b64_tr_b16 %0, %2 offset:4096\n\tds_read_b64_tr_b16 %1, %3 offset:4096" : "=v"(t0), "=v"(t1) : "v"(b0), "v"(b1)); break;
-        case 2: asm volatile("ds_read_b64_tr_b16 %0, %2 offset:8192\n\tds_read_b64_tr_b16 %1, %3 offset:8192" : "=v"(t0), "=v"(t1) : "v"(b0), "v"(b1)); break;
-        default: asm volatile("ds_read_b64_tr_b16 %0, %2 offset:12288\n\tds_read_b64_tr_b16 %1, %3 offset:12288" : "=v"(t0), "=v"(t1) : "v"(b0), "v"(b1)); break;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t0), "+v"(t1));
-      unsigned short* o = out + ((ds * 4 + ks) * 64 + lane) * 8;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) { o[x] = (unsigned short)t0[x]; o[4 + x] = (unsigned short)t1[x]; }
-    }
-  }
-}
-
-at::Tensor tr_probe() {
-  auto out = at::empty({4, 4, 64, 8},
-                       at::TensorOptions().dtype(at::kShort).device(at::kCUDA));
-  hipLaunchKernelGGL(tr_probe_kernel, dim3(1), dim3(64), 0, cur_stream(),
-                     (unsigned short*)out.data_ptr());
-  return out;
-}
-
-at::Tensor permlane_probe() {
-  auto out = at::empty({64}, at::TensorOptions().dtype(at::kInt).device(at::kCUDA));
-  hipLaunchKernelGGL(permlane_probe_kernel, dim3(1), dim3(64), 0, cur_stream(),
-                     out.data_ptr<int>());
-  return out;
-}
-
-std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                               double scale) {
-  // q: [B,Hq,S,D]; k,v: [B,Hkv,S,D]; causal, D=128, S % 256 == 0
-  check_bf16_contig(q, "q");
-  check_bf16_contig(k, "k");
-  check_bf16_contig(v, "v");
-  int B = (int)q.size(0), Hq = (int)q.size(1), S = (int)q.size(2), D = (int)q.size(3);
-  int Hkv = (int)k.size(1);
-  TORCH_CHECK(D == FF_D, "fa_fwd supports head_dim 128");
-  TORCH_CHECK(S % FF_QTILE == 0, "seq must be a multiple of 256");
-  TORCH_CHECK(Hq % Hkv == 0, "Hq must be a multiple of Hkv");
+std::vector<at::Tensor> fa_fwd_impl(const Binding& b, int64_t mode, at::Tensor q,
+                                    at::Tensor k, at::Tensor v, double scale) {
+  FaShape s = fa_check(b, FF_QTILE, q, k, v);
   auto out = at::empty_like(q);
-  auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  dim3 grid(S / FF_QTILE, Hq, B);
-  hipLaunchKernelGGL(fa_fwd_bf16, grid, dim3(FF_THREADS), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (unsigned short*)out.data_ptr(), lse.data_ptr<float>(),
-                     B, Hq, Hkv, S, (float)scale);
+  auto lse = at::empty({s.B, s.Hq, s.S}, q.options().dtype(F32));
+  decltype(&fa_fwd_bf16) kerns[] = {fa_fwd_bf16,     fa_fwd_bf16_ab1, fa_fwd_bf16_ab2,
+                                    fa_fwd_bf16_ab3, fa_fwd_bf16_ab4, fa_fwd_bf16_ab5};
+  b.launch(kerns[mode], dim3(s.S / FF_QTILE, s.Hq, s.B), FF_THREADS, bf16(q), bf16(k), bf16(v),
+           bf16_mut(out), lse.data_ptr<float>(), s.B, s.Hq, s.Hkv, s.S, (float)scale);
   return {out, lse};
+}
+
+std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale) {
+  return fa_fwd_impl(Binding("fa_fwd", "q", q), 0, q, k, v, scale);
 }
 
 std::vector<at::Tensor> fa_fwd_ablate(at::Tensor q, at::Tensor k, at::Tensor v,
                                       double scale, int64_t mode) {
   // ablation-timing variants of fa_fwd (NOT numerically meaningful for
   // mode != 0); see attention_fwd.hip template MODE docs
-  int B = (int)q.size(0), Hq = (int)q.size(1), S = (int)q.size(2);
-  int Hkv = (int)k.size(1);
-  auto out = at::empty_like(q);
-  auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  dim3 grid(S / FF_QTILE, Hq, B);
-  auto kern = mode == 1 ? fa_fwd_bf16_ab1 : mode == 2 ? fa_fwd_bf16_ab2
-              : mode == 3 ? fa_fwd_bf16_ab3 : mode == 4 ? fa_fwd_bf16_ab4
-              : mode == 5 ? fa_fwd_bf16_ab5 : fa_fwd_bf16;
-  hipLaunchKernelGGL(kern, grid, dim3(FF_THREADS), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (unsigned short*)out.data_ptr(), lse.data_ptr<float>(),
-                     B, Hq, Hkv, S, (float)scale);
-  return {out, lse};
+  TORCH_CHECK(mode >= 0 && mode <= 5, "fa_fwd_ablate: mode = ", mode,
+              " must be in 0..5");
+  return fa_fwd_impl(Binding("fa_fwd_ablate", "q", q), mode, q, k, v, scale);
+}
+
+// delta[row] = sum_d dout * o, shared by both tuned backwards
+at::Tensor fa_bwd_delta(const Binding& b, const FaShape& s, const at::Tensor& dout,
+                        const at::Tensor& o) {
+  auto delta = at::empty({s.B, s.Hq, s.S}, o.options().dtype(F32));
+  int64_t rows = (int64_t)s.B * s.Hq * s.S;
+  b.launch(fa_bwd_preprocess, grid_for(rows, 1, 4096), 256, bf16(dout), bf16(o),
+           delta.data_ptr<float>(), rows);
+  return delta;
+}
+
+// [B,Hq,S,D] per-q-head partial -> [B,Hkv,S,D] (identity when Hkv == Hq)
+at::Tensor fa_bwd_reduce(const Binding& b, const FaShape& s, const at::Tensor& part) {
+  if (s.Hkv == s.Hq) return part;
+  auto out = at::empty({s.B, s.Hkv, s.S, FF_D}, part.options());
+  int64_t SD = (int64_t)s.S * FF_D;
+  b.launch(fa_bwd_reduce_gqa, grid_for((int64_t)s.B * s.Hkv * SD / 8, 256), 256,
+           bf16(part), bf16_mut(out), s.B, s.Hq, s.Hkv, SD);
+  return out;
+}
+
+// ------------------------------ flash-attention backward -------------------
+std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                               at::Tensor dout, at::Tensor lse, double scale) {
+  Binding b("fa_bwd", "q", q);
+  FaShape s = fa_check(b, FA_BLK, q, k, v, o, dout, lse);
+  auto delta = fa_bwd_delta(b, s, dout, o);
+  auto dq = at::empty_like(q);
+  auto dk_part = at::empty_like(q);
+  auto dv_part = at::empty_like(q);
+  dim3 gridkv(s.S / FA_BLK, s.Hq, s.B);
+  b.launch(fa_bwd_dkdv, gridkv, FA_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+           lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dk_part),
+           bf16_mut(dv_part), s.B, s.Hq, s.Hkv, s.S, (float)scale);
+  b.launch(fa_bwd_dq, gridkv, FA_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+           lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), s.B, s.Hq,
+           s.Hkv, s.S, (float)scale);
+  return {dq, fa_bwd_reduce(b, s, dk_part), fa_bwd_reduce(b, s, dv_part)};
 }
 
 // ------------------------------ flash-attention backward v2 ---------------
-std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v,
-                                at::Tensor o, at::Tensor dout, at::Tensor lse,
-                                double scale, bool fused_dvdk) {
+std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                at::Tensor dout, at::Tensor lse, double scale,
+                                bool fused_dvdk) {
   // 32x32-MFMA backward (attention_bwd2.hip): preprocess + dq + dv + dk
-  // (+ GQA reduction). q,o,dout: [B,Hq,S,D]; k,v: [B,Hkv,S,D]; lse ln-dom.
-  check_bf16_contig(q, "q");
-  check_bf16_contig(k, "k");
-  check_bf16_contig(v, "v");
-  check_bf16_contig(o, "o");
-  int B = (int)q.size(0), Hq = (int)q.size(1), S = (int)q.size(2), D = (int)q.size(3);
-  int Hkv = (int)k.size(1);
-  TORCH_CHECK(D == FB_D, "fa_bwd2 supports head_dim 128");
-  TORCH_CHECK(S % FB_TILE == 0, "seq must be a multiple of 128");
-  TORCH_CHECK(lse.scalar_type() == at::kFloat);
-  auto lse_c = lse.contiguous();
-  auto dout_c = dout.contiguous();
-  auto delta = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  int64_t rows = (int64_t)B * Hq * S;
-  hipLaunchKernelGGL(fa_bwd_preprocess, dim3(grid_for(rows, 1, 4096)), dim3(256),
-                     0, cur_stream(),
-                     (const unsigned short*)dout_c.data_ptr(),
-                     (const unsigned short*)o.data_ptr(),
-                     delta.data_ptr<float>(), rows);
+  // (+ GQA reduction); lse ln-domain.
+  Binding b("fa_bwd2", "q", q);
+  FaShape s = fa_check(b, FB_TILE, q, k, v, o, dout, lse);
+  auto delta = fa_bwd_delta(b, s, dout, o);
   auto dq = at::empty_like(q);
-  dim3 grid(S / FB_TILE, Hq, B);
-  hipLaunchKernelGGL(fa2_dq_bf16, grid, dim3(FB_THREADS), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (const unsigned short*)dout_c.data_ptr(),
-                     lse_c.data_ptr<float>(), delta.data_ptr<float>(),
-                     (unsigned short*)dq.data_ptr(), B, Hq, Hkv, S,
-                     (float)scale);
-  auto dv_part = at::empty({B, Hq, S, D}, q.options());
-  auto dk_part = at::empty({B, Hq, S, D}, q.options());
+  dim3 grid(s.S / FB_TILE, s.Hq, s.B);
+  b.launch(fa2_dq_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+           lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), s.B, s.Hq,
+           s.Hkv, s.S, (float)scale);
+  auto dv_part = at::empty_like(q);
+  auto dk_part = at::empty_like(q);
   if (fused_dvdk) {
     // 4-wave blocks over 128-row kv tiles (see kernel comment): 2x the
     // blocks of the split kernels' 256-row tiles.
-    dim3 gridf(S / FD_TILE, Hq, B);
-    hipLaunchKernelGGL(fa2_dvdk_bf16, gridf, dim3(FD_THREADS), 0, cur_stream(),
-                       (const unsigned short*)q.data_ptr(),
-                       (const unsigned short*)k.data_ptr(),
-                       (const unsigned short*)v.data_ptr(),
-                       (const unsigned short*)dout_c.data_ptr(),
-                       lse_c.data_ptr<float>(), delta.data_ptr<float>(),
-                       (unsigned short*)dv_part.data_ptr(),
-                       (unsigned short*)dk_part.data_ptr(), B, Hq, Hkv, S,
-                       (float)scale);
+    b.launch(fa2_dvdk_bf16, dim3(s.S / FD_TILE, s.Hq, s.B), FD_THREADS, bf16(q),
+             bf16(k), bf16(v), bf16(dout), lse.data_ptr<float>(),
+             delta.data_ptr<float>(), bf16_mut(dv_part), bf16_mut(dk_part), s.B, s.Hq,
+             s.Hkv, s.S, (float)scale);
   } else {
-    hipLaunchKernelGGL(fa2_dv_bf16, grid, dim3(FB_THREADS), 0, cur_stream(),
-                       (const unsigned short*)q.data_ptr(),
-                       (const unsigned short*)k.data_ptr(),
-                       (const unsigned short*)dout_c.data_ptr(),
-                       lse_c.data_ptr<float>(),
-                       (unsigned short*)dv_part.data_ptr(), B, Hq, Hkv, S,
-                       (float)scale);
-    hipLaunchKernelGGL(fa2_dk_bf16, grid, dim3(FB_THREADS), 0, cur_stream(),
-                       (const unsigned short*)q.data_ptr(),
-                       (const unsigned short*)k.data_ptr(),
-                       (const unsigned short*)v.data_ptr(),
-                       (const unsigned short*)dout_c.data_ptr(),
-                       lse_c.data_ptr<float>(), delta.data_ptr<float>(),
-                       (unsigned short*)dk_part.data_ptr(), B, Hq, Hkv, S,
-                       (float)scale);
+    b.launch(fa2_dv_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(dout),
+             lse.data_ptr<float>(), bf16_mut(dv_part), s.B, s.Hq, s.Hkv, s.S,
+             (float)scale);
+    b.launch(fa2_dk_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+             lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dk_part), s.B,
+             s.Hq, s.Hkv, s.S, (float)scale);
   }
-  at::Tensor dk, dv;
-  if (Hkv == Hq) {
-    dk = dk_part;
-    dv = dv_part;
-  } else {
-    dk = at::empty({B, Hkv, S, D}, q.options());
-    dv = at::empty({B, Hkv, S, D}, q.options());
-    int64_t SD = (int64_t)S * D;
-    int rgrid = grid_for((int64_t)B * Hkv * SD / 8, 256);
-    hipLaunchKernelGGL(fa_bwd_reduce_gqa, dim3(rgrid), dim3(256), 0,
-                       cur_stream(),
-                       (const unsigned short*)dk_part.data_ptr(),
-                       (unsigned short*)dk.data_ptr(), B, Hq, Hkv, SD);
-    hipLaunchKernelGGL(fa_bwd_reduce_gqa, dim3(rgrid), dim3(256), 0,
-                       cur_stream(),
-                       (const unsigned short*)dv_part.data_ptr(),
-                       (unsigned short*)dv.data_ptr(), B, Hq, Hkv, SD);
-  }
-  return {dq, dk, dv};
+  return {dq, fa_bwd_reduce(b, s, dk_part), fa_bwd_reduce(b, s, dv_part)};
 }
 
 // ------------------------------ general-shape flash attention --------------
-struct FaGenShape {
-  int B, Hq, Hkv, Sq, Sk, D, shift;
-};
+struct FaGenShape { int B, Hq, Hkv, Sq, Sk, D, shift; };
 
-FaGenShape fa_gen_check(const at::Tensor& q, const at::Tensor& k,
+FaGenShape fa_gen_check(const Binding& b, const at::Tensor& q, const at::Tensor& k,
                         const at::Tensor& v, bool causal, int64_t shift) {
-  check_bf16_contig(q, "q");
-  check_bf16_contig(k, "k");
-  check_bf16_contig(v, "v");
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
-              "q, k, v must be [B, H, S, D]");
+              b.fn, ": q, k, v must be [B, H, S, D]");
   int64_t D = q.size(3);
-  TORCH_CHECK(D == 64 || D == 128, "fa_gen supports head_dim 64 and 128");
-  TORCH_CHECK(k.size(3) == D && v.sizes() == k.sizes(),
-              "k, v must be [B, Hkv, Sk, D] with q's D");
-  TORCH_CHECK(k.size(0) == q.size(0), "batch dims of q and k/v differ");
+  TORCH_CHECK(D == 64 || D == 128, b.fn, ": fa_gen supports head_dim 64 and 128");
   TORCH_CHECK(k.size(1) >= 1 && q.size(1) % k.size(1) == 0,
-              "Hq must be a multiple of Hkv");
-  TORCH_CHECK(q.size(2) >= 1 && k.size(2) >= 1, "Sq and Sk must be >= 1");
+              b.fn, ": Hq must be a multiple of Hkv");
+  TORCH_CHECK(q.size(2) >= 1 && k.size(2) >= 1, b.fn, ": Sq and Sk must be >= 1");
   TORCH_CHECK(q.size(0) >= 1 && q.size(0) <= 65535 && q.size(1) <= 65535,
-              "B and Hq must be in [1, 65535]");
-  TORCH_CHECK(q.size(2) + k.size(2) < (int64_t)1 << 30, "sequence too long");
-  TORCH_CHECK(causal || shift == 0, "shift needs causal");
+              b.fn, ": B and Hq must be in [1, 65535]");
+  TORCH_CHECK(q.size(2) + k.size(2) < (int64_t)1 << 30, b.fn, ": sequence too long");
+  TORCH_CHECK(causal || shift == 0, b.fn, ": shift needs causal");
+  b.arg("q", q, BF16);
+  b.arg("k", k, BF16, {q.size(0), -1, -1, D});  // [B, Hkv, Sk, D]
+  b.arg("v", v, BF16, k.sizes());
   // clamping to [-Sq, Sk] leaves the mask j <= i + shift unchanged
   int64_t sh = std::max<int64_t>(-q.size(2), std::min<int64_t>(k.size(2), shift));
   return {(int)q.size(0), (int)q.size(1), (int)k.size(1), (int)q.size(2),
           (int)k.size(2), (int)D, (int)sh};
 }
 
+// The one place that picks a general kernel's head-dim instantiation.
+#define FA_GEN_KERNEL(kernel, D) ((D) == 64 ? kernel<64> : kernel<128>)
+
 std::vector<at::Tensor> fa_gen_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                    double scale, bool causal, int64_t shift) {
   // q: [B,Hq,Sq,D]; k,v: [B,Hkv,Sk,D] -> {o [B,Hq,Sq,D], lse [B,Hq,Sq] f32}
-  FaGenShape s = fa_gen_check(q, k, v, causal, shift);
+  Binding b("fa_gen_fwd", "q", q);
+  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift);
   auto out = at::empty_like(q);
-  auto lse = at::empty({s.B, s.Hq, s.Sq}, q.options().dtype(at::kFloat));
-  dim3 grid((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B);
-  auto kern = s.D == 64 ? fa_gen_fwd_kernel<64> : fa_gen_fwd_kernel<128>;
-  hipLaunchKernelGGL(kern, grid, dim3(FG_THREADS), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (unsigned short*)out.data_ptr(), lse.data_ptr<float>(),
-                     s.Hq, s.Hkv, s.Sq, s.Sk, (float)(scale * 1.4426950408889634),
-                     causal ? 1 : 0, s.shift);
+  auto lse = at::empty({s.B, s.Hq, s.Sq}, q.options().dtype(F32));
+  b.launch(FA_GEN_KERNEL(fa_gen_fwd_kernel, s.D),
+           dim3((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B), FG_THREADS, bf16(q), bf16(k),
+           bf16(v), bf16_mut(out), lse.data_ptr<float>(), s.Hq, s.Hkv, s.Sq, s.Sk,
+           (float)(scale * 1.4426950408889634), causal ? 1 : 0, s.shift);
   return {out, lse};
 }
 
 std::vector<at::Tensor> fa_gen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                    at::Tensor o, at::Tensor dout, at::Tensor lse,
-                                   c10::optional<at::Tensor> dlse, double scale,
-                                   bool causal, int64_t shift) {
-  FaGenShape s = fa_gen_check(q, k, v, causal, shift);
-  check_bf16_contig(o, "o");
-  check_bf16_contig(dout, "dout");
-  TORCH_CHECK(o.sizes() == q.sizes() && dout.sizes() == q.sizes(),
-              "o and dout must have q's shape");
-  auto check_row = [&](const at::Tensor& t, const char* name) {
-    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() &&
-                    t.dim() == 3 && t.size(0) == s.B && t.size(1) == s.Hq &&
-                    t.size(2) == s.Sq,
-                name, " must be contiguous fp32 [B, Hq, Sq] on device");
-  };
-  check_row(lse, "lse");
-  const float* dlse_p = nullptr;
-  if (dlse.has_value()) {
-    check_row(*dlse, "dlse");
-    dlse_p = dlse->data_ptr<float>();
-  }
-  auto delta = at::empty({s.B, s.Hq, s.Sq}, q.options().dtype(at::kFloat));
+                                   OptTensor dlse, double scale, bool causal,
+                                   int64_t shift) {
+  Binding b("fa_gen_bwd", "q", q);
+  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift);
+  b.arg("o", o, BF16, q.sizes());
+  b.arg("dout", dout, BF16, q.sizes());
+  b.arg("lse", lse, F32, {s.B, s.Hq, s.Sq});
+  b.arg("dlse", dlse, F32, {s.B, s.Hq, s.Sq});
+  auto delta = at::empty({s.B, s.Hq, s.Sq}, q.options().dtype(F32));
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
   int64_t rows = (int64_t)s.B * s.Hq * s.Sq;
-  auto pre = s.D == 64 ? fa_gen_preprocess_kernel<64> : fa_gen_preprocess_kernel<128>;
-  hipLaunchKernelGGL(pre, dim3(grid_for(rows, 256 / (s.D / 8), 4096)), dim3(256),
-                     0, cur_stream(), (const unsigned short*)dout.data_ptr(),
-                     (const unsigned short*)o.data_ptr(), lse.data_ptr<float>(),
-                     dlse_p, delta.data_ptr<float>(), rows);
-  auto kkv = s.D == 64 ? fa_gen_dkdv_kernel<64> : fa_gen_dkdv_kernel<128>;
-  dim3 gridkv((s.Sk + FG_BLK - 1) / FG_BLK, s.Hkv, s.B);
-  hipLaunchKernelGGL(kkv, gridkv, dim3(FG_THREADS), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (const unsigned short*)dout.data_ptr(),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(),
-                     (unsigned short*)dk.data_ptr(),
-                     (unsigned short*)dv.data_ptr(), s.Hq, s.Hkv, s.Sq, s.Sk,
-                     (float)scale, causal ? 1 : 0, s.shift);
-  auto kq = s.D == 64 ? fa_gen_dq_kernel<64> : fa_gen_dq_kernel<128>;
-  dim3 gridq((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B);
-  hipLaunchKernelGGL(kq, gridq, dim3(FG_THREADS), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (const unsigned short*)dout.data_ptr(),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(),
-                     (unsigned short*)dq.data_ptr(), s.Hq, s.Hkv, s.Sq, s.Sk,
-                     (float)scale, causal ? 1 : 0, s.shift);
+  b.launch(FA_GEN_KERNEL(fa_gen_preprocess_kernel, s.D),
+           grid_for(rows, 256 / (s.D / 8), 4096), 256, bf16(dout), bf16(o),
+           lse.data_ptr<float>(), f32(dlse), delta.data_ptr<float>(), rows);
+  b.launch(FA_GEN_KERNEL(fa_gen_dkdv_kernel, s.D),
+           dim3((s.Sk + FG_BLK - 1) / FG_BLK, s.Hkv, s.B), FG_THREADS, bf16(q), bf16(k),
+           bf16(v), bf16(dout), lse.data_ptr<float>(), delta.data_ptr<float>(),
+           bf16_mut(dk), bf16_mut(dv), s.Hq, s.Hkv, s.Sq, s.Sk, (float)scale,
+           causal ? 1 : 0, s.shift);
+  b.launch(FA_GEN_KERNEL(fa_gen_dq_kernel, s.D),
+           dim3((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B), FG_THREADS, bf16(q), bf16(k),
+           bf16(v), bf16(dout), lse.data_ptr<float>(), delta.data_ptr<float>(),
+           bf16_mut(dq), s.Hq, s.Hkv, s.Sq, s.Sk, (float)scale, causal ? 1 : 0,
+           s.shift);
   return {dq, dk, dv};
 }
 
 // ------------------------------ philox random ------------------------------
-ShardDesc make_desc(const std::vector<int64_t>& gshape,
-                    const std::vector<int64_t>& lshape,
-                    const std::vector<int64_t>& offset, int64_t flat_offset,
-                    bool is_flat) {
+using Dims = std::vector<int64_t>;
+
+// Shard descriptor for a local tensor of `numel` elements.
+ShardDesc make_desc(const char* fn, const Dims& gshape, const Dims& lshape,
+                    const Dims& offset, int64_t flat_offset, bool is_flat,
+                    int64_t numel) {
+  TORCH_CHECK(gshape.size() <= MAXD && lshape.size() == gshape.size() &&
+                  offset.size() == gshape.size(),
+              fn, ": gshape, lshape, offset must have one length <= ", MAXD,
+              ", got ", gshape.size(), ", ", lshape.size(), ", ", offset.size());
   ShardDesc d{};
   d.ndim = (int)gshape.size();
-  TORCH_CHECK(d.ndim <= MAXD);
+  int64_t prod = 1;
   for (int i = 0; i < d.ndim; ++i) {
     d.gshape[i] = gshape[i];
     d.lshape[i] = lshape[i];
     d.offset[i] = offset[i];
+    prod *= lshape[i];
   }
+  TORCH_CHECK(prod == numel, fn, ": prod(lshape) = ", prod,
+              " must equal the tensor's numel = ", numel);
   d.flat_offset = flat_offset;
   d.is_flat = is_flat ? 1 : 0;
   return d;
 }
 
-void philox_uniform_(at::Tensor out, std::vector<int64_t> gshape,
-                     std::vector<int64_t> lshape, std::vector<int64_t> offset,
-                     int64_t flat_offset, bool is_flat, int64_t seed,
-                     int64_t philox_offset, double lo, double hi) {
-  auto d = make_desc(gshape, lshape, offset, flat_offset, is_flat);
+// philox_uniform_(.., lo, hi) and philox_normal_(.., mean, std): one dtype dispatch.
+template <bool NORMAL>
+void philox_fill(at::Tensor out, Dims gshape, Dims lshape, Dims offset,
+                 int64_t flat_offset, bool is_flat, int64_t seed, int64_t philox_offset,
+                 double p0, double p1) {
+  Binding b(NORMAL ? "philox_normal_" : "philox_uniform_", "out", out);
   int64_t n = out.numel();
-  int grid = grid_for(n, 256);
-  if (out.scalar_type() == at::kBFloat16) {
-    hipLaunchKernelGGL(philox_uniform_bf16, dim3(grid), dim3(256), 0,
-                       cur_stream(), (unsigned short*)out.data_ptr(), d, n,
-                       (uint64_t)seed, (uint64_t)philox_offset, (float)lo,
-                       (float)hi);
-  } else {
-    hipLaunchKernelGGL(philox_uniform_f32, dim3(grid), dim3(256), 0,
-                       cur_stream(), out.data_ptr<float>(), d, n,
-                       (uint64_t)seed, (uint64_t)philox_offset, (float)lo,
-                       (float)hi);
-  }
+  auto d = make_desc(b.fn, gshape, lshape, offset, flat_offset, is_flat, n);
+  b.arg("out", out, {BF16, F32});
+  if (out.scalar_type() == BF16)
+    b.launch(NORMAL ? philox_normal_bf16 : philox_uniform_bf16, grid_for(n, 256), 256,
+             bf16_mut(out), d, n, (uint64_t)seed, (uint64_t)philox_offset, (float)p0,
+             (float)p1);
+  else
+    b.launch(NORMAL ? philox_normal_f32 : philox_uniform_f32, grid_for(n, 256), 256,
+             out.data_ptr<float>(), d, n, (uint64_t)seed, (uint64_t)philox_offset,
+             (float)p0, (float)p1);
 }
 
-void philox_normal_(at::Tensor out, std::vector<int64_t> gshape,
-                    std::vector<int64_t> lshape, std::vector<int64_t> offset,
-                    int64_t flat_offset, bool is_flat, int64_t seed,
-                    int64_t philox_offset, double mean, double std) {
-  auto d = make_desc(gshape, lshape, offset, flat_offset, is_flat);
-  int64_t n = out.numel();
-  int grid = grid_for(n, 256);
-  if (out.scalar_type() == at::kBFloat16) {
-    hipLaunchKernelGGL(philox_normal_bf16, dim3(grid), dim3(256), 0,
-                       cur_stream(), (unsigned short*)out.data_ptr(), d, n,
-                       (uint64_t)seed, (uint64_t)philox_offset, (float)mean,
-                       (float)std);
-  } else {
-    hipLaunchKernelGGL(philox_normal_f32, dim3(grid), dim3(256), 0,
-                       cur_stream(), out.data_ptr<float>(), d, n,
-                       (uint64_t)seed, (uint64_t)philox_offset, (float)mean,
-                       (float)std);
-  }
-}
-
-std::vector<at::Tensor> philox_dropout(at::Tensor x, std::vector<int64_t> gshape,
-                                       std::vector<int64_t> lshape,
-                                       std::vector<int64_t> offset,
-                                       int64_t flat_offset, bool is_flat,
-                                       int64_t seed, int64_t philox_offset,
-                                       double p, bool need_mask) {
-  check_bf16_contig(x, "x");
-  auto d = make_desc(gshape, lshape, offset, flat_offset, is_flat);
+std::vector<at::Tensor> philox_dropout(at::Tensor x, Dims gshape, Dims lshape,
+                                       Dims offset, int64_t flat_offset, bool is_flat,
+                                       int64_t seed, int64_t philox_offset, double p,
+                                       bool need_mask) {
+  Binding b("philox_dropout", "x", x);
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "philox_dropout: p = ", p, " must be in [0, 1)");
+  int64_t n = x.numel();
+  auto d = make_desc(b.fn, gshape, lshape, offset, flat_offset, is_flat, n);
+  b.arg("x", x, BF16);
   auto out = at::empty_like(x);
   at::Tensor mask;
-  unsigned char* mp = nullptr;
-  if (need_mask) {
-    mask = at::empty(x.sizes(), x.options().dtype(at::kByte));
-    mp = mask.data_ptr<unsigned char>();
-  }
-  int64_t n = x.numel();
-  int grid = grid_for(n, 256);
-  hipLaunchKernelGGL(philox_dropout_bf16, dim3(grid), dim3(256), 0,
-                     cur_stream(), (const unsigned short*)x.data_ptr(),
-                     (unsigned short*)out.data_ptr(), mp, d, n, (uint64_t)seed,
-                     (uint64_t)philox_offset, (float)p);
+  if (need_mask) mask = at::empty(x.sizes(), x.options().dtype(at::kByte));
+  b.launch(philox_dropout_bf16, grid_for(n, 256), 256, bf16(x), bf16_mut(out),
+           need_mask ? mask.data_ptr<unsigned char>() : nullptr, d, n, (uint64_t)seed,
+           (uint64_t)philox_offset, (float)p);
   if (need_mask) return {out, mask};
   return {out};
 }
@@ -878,7 +763,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("permlane_probe", &permlane_probe);
   m.def("mfma32_probe", &mfma32_probe);
   m.def("tr_probe", &tr_probe);
-  m.def("philox_uniform_", &philox_uniform_);
-  m.def("philox_normal_", &philox_normal_);
+  m.def("philox_uniform_", &philox_fill<false>);
+  m.def("philox_normal_", &philox_fill<true>);
   m.def("philox_dropout", &philox_dropout);
 }

@@ -11,7 +11,9 @@ import torch
 
 
 def _ext():
-    from . import _C, require_ext
+    """The extension module.  Its bindings validate and never copy: every
+    tensor handed to them below is made contiguous first."""
+    from . import require_ext
 
     return require_ext()
 
@@ -37,9 +39,9 @@ class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor, eps: float):
         if _use_hip(x, weight):
-            x2 = x.contiguous()
-            out, rrms = _ext().rmsnorm_fwd(x2, weight.contiguous(), eps)
-            ctx.save_for_backward(x2, weight, rrms)
+            x2, w2 = x.contiguous(), weight.contiguous()
+            out, rrms = _ext().rmsnorm_fwd(x2, w2, eps)
+            ctx.save_for_backward(x2, w2, rrms)
             ctx.eps = eps
             ctx.hip = True
             return out
@@ -97,7 +99,7 @@ class _RoPE(torch.autograd.Function):
         if _use_hip(x, table):
             ctx.hip = True
             ctx.save_for_backward(table)
-            return _ext().rope(x.contiguous(), table, pos_offset, False, False)
+            return _ext().rope(x.contiguous(), table.contiguous(), pos_offset, False, False)
         ctx.hip = False
         ctx.save_for_backward(table)
         return _rope_ref(x, table, pos_offset, False)
@@ -106,7 +108,7 @@ class _RoPE(torch.autograd.Function):
     def backward(ctx, dy: torch.Tensor):
         (table,) = ctx.saved_tensors
         if ctx.hip:
-            return _ext().rope(dy.contiguous(), table, ctx.pos_offset, True, False), None, None
+            return _ext().rope(dy.contiguous(), table.contiguous(), ctx.pos_offset, True, False), None, None
         return _rope_ref(dy, table, ctx.pos_offset, True), None, None
 
 
@@ -135,11 +137,12 @@ class _FusedAddRMSNorm(torch.autograd.Function):
     def forward(ctx, x: torch.Tensor, res, weight: torch.Tensor, eps: float):
         ctx.has_res = res is not None
         if _use_hip(x, weight) and (res is None or res.dtype == x.dtype):
+            w2 = weight.contiguous()
             out, res_new, rrms = _ext().rmsnorm_res_fwd(
                 x.contiguous(), res.contiguous() if res is not None else None,
-                weight.contiguous(), eps,
+                w2, eps,
             )
-            ctx.save_for_backward(res_new, weight, rrms)
+            ctx.save_for_backward(res_new, w2, rrms)
             ctx.hip = True
             return out, res_new
         res_new = x if res is None else (x + res)
@@ -196,7 +199,7 @@ class _RoPEQKV(torch.autograd.Function):
         if _use_hip(qkv, table):
             ctx.hip = True
             q, k, v = _ext().rope_qkv_fwd(
-                qkv.contiguous(), table, B, S, n_heads, n_kv_heads, head_dim,
+                qkv.contiguous(), table.contiguous(), B, S, n_heads, n_kv_heads, head_dim,
                 pos_offset,
             )
             return q, k, v
@@ -222,7 +225,7 @@ class _RoPEQKV(torch.autograd.Function):
         if ctx.hip:
             dqkv = _ext().rope_qkv_bwd(
                 dq.contiguous(), dk.contiguous(), dv.contiguous(),
-                table, B, S, Hq, Hkv, D, pos,
+                table.contiguous(), B, S, Hq, Hkv, D, pos,
             )
             return dqkv, None, None, None, None, None
         dq = dq.permute(0, 2, 1, 3)  # [B,H,S,D] -> [B,S,H,D]
@@ -296,7 +299,7 @@ class _SwiGLUPacked(torch.autograd.Function):
     def backward(ctx, dy: torch.Tensor):
         (gu,) = ctx.saved_tensors
         if ctx.hip:
-            return _ext().swiglu_packed_bwd(dy, gu)
+            return _ext().swiglu_packed_bwd(dy.contiguous(), gu)
         F = gu.shape[-1] // 2
         g = gu[..., :F].float()
         u = gu[..., F:].float()
@@ -319,9 +322,9 @@ class _FusedCE(torch.autograd.Function):
     def forward(ctx, logits: torch.Tensor, target: torch.Tensor, ignore_index: int):
         n_tok = (target != ignore_index).sum().clamp(min=1)
         if _use_hip(logits):
-            lg = logits.contiguous()
-            loss, lse = _ext().ce_fwd(lg, target.contiguous(), ignore_index)
-            ctx.save_for_backward(lg, target, lse, n_tok)
+            lg, tg = logits.contiguous(), target.contiguous()
+            loss, lse = _ext().ce_fwd(lg, tg, ignore_index)
+            ctx.save_for_backward(lg, tg, lse, n_tok)
             ctx.ignore_index = ignore_index
             ctx.hip = True
             return loss.sum() / n_tok.to(loss.dtype)
@@ -365,9 +368,9 @@ def fused_cross_entropy(
 
 
 # ---------------------------------------------------------------------------
-# Flash attention: library forward (returns logsumexp) + our CDNA4 MFMA
-# backward (ops/csrc/attention_bwd.hip) — the stock backward is the profiled
-# bottleneck (~255 TF effective); causal, head_dim 128, GQA.
+# Tuned flash attention: our CDNA4 MFMA forward (ops/csrc/attention_fwd.hip,
+# returns logsumexp) + backward (ops/csrc/attention_bwd2.hip); causal,
+# head_dim 128, GQA, seq % 256 == 0.
 # ---------------------------------------------------------------------------
 class _FlashAttention(torch.autograd.Function):
     """Causal flash attention, fully on our MFMA kernels: fa_fwd
@@ -393,7 +396,9 @@ class _FlashAttention(torch.autograd.Function):
         # only fits at 1 wave/SIMD (4-wave blocks), and the lost latency
         # hiding outweighs the deduplicated ST GEMM + staging.  Kept for A/B.
         fused = os.environ.get("VESCALE_FA_FUSED_DVDK", "0") == "1"
-        dq, dk, dv = _ext().fa_bwd2(q, k, v, out, dout, lse, ctx.scale, fused)
+        dq, dk, dv = _ext().fa_bwd2(
+            q, k, v, out, dout.contiguous(), lse, ctx.scale, fused
+        )
         return dq, dk, dv, None
 
 
@@ -562,7 +567,7 @@ def adamw_step_flat(
 @torch.no_grad()
 def l2norm_sq(x: torch.Tensor) -> torch.Tensor:
     if _use_hip(x):
-        return _ext().l2norm_sq(x).squeeze(0)
+        return _ext().l2norm_sq(x.contiguous()).squeeze(0)
     return x.float().pow(2).sum()
 
 
