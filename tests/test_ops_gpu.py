@@ -463,6 +463,43 @@ def test_flash_attention_bwd_kernel():
 
 
 @requires_gpu
+def test_flash_attention_bwd2_split_and_fused():
+    """fa_fwd -> fa_bwd2 (attention_bwd2.hip) with the split fa2_dv/fa2_dk
+    kernels and with the fused fa2_dvdk kernel, each vs SDPA autograd.
+    S=512 is the smallest S (gate: S % 256) at which the split kernels get
+    a second kv block, one that starts off the diagonal; the fused kernel
+    gets four blocks; every kernel has waves that are inactive on some
+    tiles and masked on others.  Hq=2, Hkv=1 runs the GQA reduce.
+    Tolerances are test_flash_attention_bwd_kernel's."""
+    import math
+
+    import torch.nn.functional as F
+
+    import vescale_amd.ops as ops
+
+    C = ops.require_ext()
+    torch.manual_seed(17)
+    B, Hq, Hkv, S, D = 1, 2, 1, 512, 128
+    q = torch.randn(B, Hq, S, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    k = torch.randn(B, Hkv, S, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    v = torch.randn(B, Hkv, S, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    dy = torch.randn(B, Hq, S, D, device="cuda", dtype=torch.bfloat16)
+    sc = 1.0 / math.sqrt(D)
+    ref = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=True)
+    ref.backward(dy)
+    qd, kd, vd = q.detach(), k.detach(), v.detach()
+    o, lse = C.fa_fwd(qd, kd, vd, sc)
+    assert not torch.isnan(o).any() and not torch.isnan(lse).any()
+    for fused in (False, True):
+        dq, dk, dv = C.fa_bwd2(qd, kd, vd, o, dy, lse, sc, fused)
+        for name, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+            assert not torch.isnan(t).any(), (fused, name)
+        assert torch.allclose(dq.float(), q.grad.float(), atol=6e-2, rtol=8e-2), fused
+        assert torch.allclose(dk.float(), k.grad.float(), atol=8e-2, rtol=1e-1), fused
+        assert torch.allclose(dv.float(), v.grad.float(), atol=8e-2, rtol=1e-1), fused
+
+
+@requires_gpu
 def test_sharded_dropout_bitwise_tp_parity():
     """End-to-end headline RNG property through DTensor dispatch: dropout
     on a SHARDED DTensor is bitwise-identical to the same dropout on the

@@ -31,52 +31,14 @@
 //     library's) can consume it.
 // Capability parity: reference vescale relies on library flash attention;
 // this is the MI355X-native forward for the train step's hot op.
-#include "common.h"
+#include "fa32_common.h"
 
-#define FF_D 128
 #define FF_QBLK 32             // q rows per wave
 #define FF_WAVES 4
-#define FF_QTILE (FF_QBLK * FF_WAVES)  // 256 q rows per block
+#define FF_QTILE (FF_QBLK * FF_WAVES)  // 128 q rows per block
 #define FF_KV 64               // kv tile
 #define FF_THREADS (FF_WAVES * 64)
-
-typedef float ff_floatx4 __attribute__((ext_vector_type(4)));
-typedef float ff_floatx16 __attribute__((ext_vector_type(16)));
-typedef short ff_shortx4 __attribute__((ext_vector_type(4)));
-typedef short ff_shortx8 __attribute__((ext_vector_type(8)));
-typedef int ff_intx4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) const unsigned short* ff_lds_p;
-
-// partner-half exchange: returns the value this VGPR holds in lane l^32.
-// permlane32_swap(a,b) returns the post-swap pair: r0 = [a:0-31 | b:0-31],
-// r1 = [a:32-63 | b:32-63] (probe-verified: tools/fa_fwd_check.py — lane 0
-// sees partner in r1, lane 32 sees partner in r0).
-DEV int ff_swap_other(int x, int half) {
-  auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return half ? r[0] : r[1];
-}
-
-// XCD-aware block remap (guide T1): the 8 XCDs have private L2s and the
-// HW round-robins consecutive workgroups across them; remapping so each
-// XCD owns a CONTIGUOUS chunk of the flat grid keeps all q-tiles of the
-// same (batch, head) — which stream the same K/V — on one XCD's L2.
-// Bijective when nwg % 8 == 0 (else identity).
-DEV void ff_xcd_remap(int& bx, int& by, int& bz) {
-  int gx = gridDim.x, gy = gridDim.y;
-  int nwg = gx * gy * (int)gridDim.z;
-  if ((nwg & 7) != 0) return;
-  int f = bx + gx * (by + gy * bz);
-  f = (f & 7) * (nwg >> 3) + (f >> 3);
-  bx = f % gx; f /= gx;
-  by = f % gy;
-  bz = f / gy;
-}
-
-// K-tile LDS swizzle (guide G4): XOR byte-bits 4-6 slot with row bits 0-2
-DEV int ff_kswz(int byte_off) {
-  int row = byte_off >> 8;  // 256B rows ([64][128] bf16)
-  return byte_off ^ ((row & 7) << 4);
-}
+#define FF_CHUNKS FF_STAGE_CHUNKS(FF_KV, FF_THREADS)  // staging chunks per thread per tile
 
 template <int MODE>  // 0=full, 1=no-softmax, 2=no-PV, 3=no-ST, 4=no-gating, 5=exp-domain (bisect)
 DEV void fa_fwd_t(const unsigned short* __restrict__ q,
@@ -88,66 +50,47 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
   __shared__ unsigned short lk[2][FF_KV * FF_D];  // K, swizzled
   __shared__ unsigned short lv[2][FF_KV * FF_D];  // V, swizzled (same as K)
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int l31 = lane & 31;
-  const int half = lane >> 5;  // 0 | 1
-  const int g16 = lane >> 4;   // 16-lane group, for tr reads
-
-  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  ff_xcd_remap(bx, by, bz);
-  const int qt = bx;               // q macro-tile
-  const int h = by;
-  const int b = bz;
-  const int hkv = h / (Hq / Hkv);
-
-  const int64_t qbase = (((int64_t)b * Hq + h) * S) * FF_D;
-  const int64_t kbase = (((int64_t)b * Hkv + hkv) * S) * FF_D;
-  const int q0 = qt * FF_QTILE + wave * FF_QBLK;   // wave's first q row
-  const int my_q = q0 + l31;                        // this lane's q row
-  const float scale2 = (MODE == 5) ? scale : scale * 1.44269504088896340736f;
+  const ff_ctx c = ff_prologue(Hq, Hkv, S);
+  const int tid = c.tid, lane = c.lane, l31 = c.l31, half = c.half;
+  const int qt = c.tile;                             // q macro-tile
+  const int q0 = qt * FF_QTILE + c.wave * FF_QBLK;   // wave's first q row
+  const int my_q = q0 + l31;                         // this lane's q row
+  const float scale2 = (MODE == 5) ? scale : scale * FF_LOG2E;
 
   // ---- Q fragments in registers: B-operand B[j=q][k=d] ----
   // lane holds Q[my_q][ (half*8 + e) + 16*ks ] for ks = 0..7
   ff_shortx8 qf[8];
-  {
-    const unsigned short* qg = q + qbase + (int64_t)my_q * FF_D;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-      qf[ks] = *reinterpret_cast<const ff_shortx8*>(qg + ks * 16 + half * 8);
-  }
+  ff_row_frags(q + c.qbase + (int64_t)my_q * FF_D, qf, half);
 
   // ---- online-softmax state (per q = l31; replicated across halves) ----
   float m_run = -INFINITY;
   float l_run = 0.f;
   // O accumulator: 4 d-subtiles (32 d each) in D-layout:
-  //   acc[ds] reg r holds O[d = ds*32 + (r&3)+8*(r>>2)+4*half][q=l31]
+  //   acc[ds] reg r holds O[d = ff_drow(ds*32, r, half)][q=l31]
   ff_floatx16 oacc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) oacc[i] = (ff_floatx16)(0.f);
 
-  // BLOCK-UNIFORM kv loop bound (all 8 waves hit the same barriers):
-  // cover kv < (qt+1)*256, i.e. through the block's last causal tile.
+  // BLOCK-UNIFORM kv loop bound (all 4 waves hit the same barriers):
+  // cover kv < (qt+1)*128, i.e. through the block's last causal tile.
   const int n_kv = (qt + 1) * (FF_QTILE / FF_KV);
   const int last_kv = min(n_kv, S / FF_KV);
 
-  const unsigned short* kg = k + kbase;
-  const unsigned short* vg = v + kbase;
+  const unsigned short* kg = k + c.kbase;
+  const unsigned short* vg = v + c.kbase;
   // staging registers: tile elems / threads / 8 chunks per thread
-#define FF_CHUNKS (FF_KV * FF_D / (FF_THREADS * 8))
   ff_shortx8 kreg[FF_CHUNKS], vreg[FF_CHUNKS];
 #pragma unroll
   for (int j = 0; j < FF_CHUNKS; ++j) {
-    int e = (tid + j * FF_THREADS) * 8;
-    kreg[j] = *reinterpret_cast<const ff_shortx8*>(kg + e);
-    vreg[j] = *reinterpret_cast<const ff_shortx8*>(vg + e);
+    const int e = ff_chunk<FF_THREADS>(j, tid);
+    kreg[j] = ff_chunk_load(kg, e);
+    vreg[j] = ff_chunk_load(vg, e);
   }
 #pragma unroll
   for (int j = 0; j < FF_CHUNKS; ++j) {
-    int e = (tid + j * FF_THREADS) * 8;
-    *reinterpret_cast<ff_shortx8*>((char*)lk[0] + ff_kswz(e * 2)) = kreg[j];
-    *reinterpret_cast<ff_shortx8*>((char*)lv[0] + ff_kswz(e * 2)) = vreg[j];
+    const int e = ff_chunk<FF_THREADS>(j, tid);
+    ff_chunk_store(kreg[j], lk[0], e);
+    ff_chunk_store(vreg[j], lv[0], e);
   }
   __syncthreads();
 
@@ -168,9 +111,9 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
       const unsigned short* vn = vg + (int64_t)(kv0 + FF_KV) * FF_D;
 #pragma unroll
       for (int j = 0; j < FF_CHUNKS; ++j) {
-        int e = (tid + j * FF_THREADS) * 8;
-        kreg[j] = *reinterpret_cast<const ff_shortx8*>(kn + e);
-        vreg[j] = *reinterpret_cast<const ff_shortx8*>(vn + e);
+        const int e = ff_chunk<FF_THREADS>(j, tid);
+        kreg[j] = ff_chunk_load(kn, e);
+        vreg[j] = ff_chunk_load(vn, e);
       }
     }
 
@@ -185,9 +128,7 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) {
         // A-frag: K rows (s2*32 + l31), d = ks*16 + half*8 .. +8
-        int byte = ((s2 * 32 + l31) * FF_D + ks * 16 + half * 8) * 2;
-        ff_shortx8 kf = *reinterpret_cast<const ff_shortx8*>(
-            (const char*)lk[buf] + ff_kswz(byte));
+        ff_shortx8 kf = ff_afrag(lk[buf], s2, ks, l31, half);
         st[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], st[s2], 0, 0, 0);
       }
     }
@@ -197,7 +138,7 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
       l_run += 1.f; m_run = 0.f;
     } else {
     // ---- causal mask + online softmax, exp2 domain (per q = l31) ----
-    // lane holds ST[kv][q=l31] at kv = s2*32 + (r&3)+8*(r>>2)+4*half.
+    // lane holds ST[kv][q=l31] at kv = ff_drow(kv0 + s2*32, r, half).
     // Work in log2: x2 = s * scale*log2(e); p = exp2(x2 - m2) maps to a
     // bare v_exp_f32 (no hidden 1/ln2 multiply per element).
     float pmax = -INFINITY;
@@ -206,7 +147,7 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          int kv = kv0 + s2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          int kv = ff_drow(kv0 + s2 * 32, r, half);
           float x = (kv <= my_q) ? st[s2][r] * scale2 : -INFINITY;
           st[s2][r] = x;
           pmax = fmaxf(pmax, x);
@@ -258,87 +199,20 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
 #pragma unroll
       for (int r = 0; r < 16; ++r) oacc[0][r] += st[0][r] + st[1][r];
     } else {
-    // ---- P relayout to PV B-operand via cvt_pk + permlane32_swap ----
-    // Derivation (32x32 D-layout, regs r: kv_local = (r&3)+8*(r>>2)+4*half):
-    //   group g (16 kv): own regs g*8+0..3 -> kv g*16 + (0..3)+4*half ("LO")
-    //                    own regs g*8+4..7 -> kv g*16 + (8..11)+4*half ("HI")
-    //   B-frag wants kv = g*16 + half*8 + e:
-    //     half=0: e0-3 = own LO, e4-7 = partner LO (their +4..7)
-    //     half=1: e0-3 = partner HI (their 8..11), e4-7 = own HI (12..15)
-    ff_shortx8 pb[4];  // 4 ksteps of 16 kv (KV=64)
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        unsigned lo0, lo1, hi0, hi1;
-        asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo0)
-                     : "v"(st[s2][g * 8 + 0]), "v"(st[s2][g * 8 + 1]));
-        asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo1)
-                     : "v"(st[s2][g * 8 + 2]), "v"(st[s2][g * 8 + 3]));
-        asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi0)
-                     : "v"(st[s2][g * 8 + 4]), "v"(st[s2][g * 8 + 5]));
-        asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi1)
-                     : "v"(st[s2][g * 8 + 6]), "v"(st[s2][g * 8 + 7]));
-        int p0 = ff_swap_other((int)lo0, half);  // partner's LO word0
-        int p1 = ff_swap_other((int)lo1, half);  // partner's LO word1
-        int p2 = ff_swap_other((int)hi0, half);  // partner's HI word0
-        int p3 = ff_swap_other((int)hi1, half);  // partner's HI word1
-        ff_intx4 frag;
-        if (half == 0) {
-          frag = (ff_intx4){(int)lo0, (int)lo1, p0, p1};
-        } else {
-          frag = (ff_intx4){p2, p3, (int)hi0, (int)hi1};
-        }
-        pb[s2 * 2 + g] = *reinterpret_cast<ff_shortx8*>(&frag);
-      }
-    }
-
-    // ---- PV: O[d][q] += V^T . P  (contraction kv, 4 ksteps of 16) ----
-    // A-frag (V^T rows d = ds*32 + l31, kv = ks*16 + half*8 + e) via the
-    // probe-measured group transpose (tools/tr_probe_check.py):
-    //   OUT[l&15][j] = IN[4j + ((l&15)>>2)][l&3]   per 16-lane group,
-    // so lane y reads V row kvbase + ((y&15)>>2) at byte column
-    // dbase + (y&3)*4 elems, and the HW hands lane l the d = ds*32 + l31
-    // column of rows kvbase..kvbase+3. Two reads (kvbase, kvbase+4) fill
-    // the 8 kv elems; ks walks rows in +16 steps = +4096 bytes, which
-    // commutes with the bits-4..6 row swizzle (row&7 unchanged).
+    // ---- P relayout to PV B-operand (4 ksteps of 16 kv, KV=64) ----
+    ff_shortx8 pb[4];
+    ff_relayout(st, pb, half);
+    // ---- PV: O[d][q] += V^T . P  (contraction kv; A-frag V^T rows
+    // d = ds*32 + l31 via tr reads of the V tile) ----
 #pragma unroll
     for (int ds = 0; ds < 4; ++ds) {
-      const int col2 = (ds * 32 + (l31 & 16) + (lane & 3) * 4) * 2;
-      const int row0 = half * 8 + ((lane & 15) >> 2);  // kv row, jj = 0
-      const int a0 = (row0 * 256 + col2) ^ ((row0 & 7) << 4);
-      const int row1 = row0 + 4;                       // jj = 1
-      const int a1 = (row1 * 256 + col2) ^ ((row1 & 7) << 4);
-      ff_lds_p b0 = (ff_lds_p)((const char*)lv[buf] + a0);
-      ff_lds_p b1 = (ff_lds_p)((const char*)lv[buf] + a1);
       ff_shortx4 t[4][2];
-      // ONE asm statement for all 8 reads + the drain: with separate
-      // statements the compiler may interpose copies of t between a read
-      // and the waitcnt, capturing the register BEFORE the LDS data lands
-      // (observed as run-to-run nondeterminism in O). Earlyclobber outputs
-      // keep the async dsts from aliasing the address registers.
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %8 offset:0\n\t"
-          "ds_read_b64_tr_b16 %1, %9 offset:0\n\t"
-          "ds_read_b64_tr_b16 %2, %8 offset:4096\n\t"
-          "ds_read_b64_tr_b16 %3, %9 offset:4096\n\t"
-          "ds_read_b64_tr_b16 %4, %8 offset:8192\n\t"
-          "ds_read_b64_tr_b16 %5, %9 offset:8192\n\t"
-          "ds_read_b64_tr_b16 %6, %8 offset:12288\n\t"
-          "ds_read_b64_tr_b16 %7, %9 offset:12288\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(t[0][0]), "=&v"(t[0][1]), "=&v"(t[1][0]), "=&v"(t[1][1]),
-            "=&v"(t[2][0]), "=&v"(t[2][1]), "=&v"(t[3][0]), "=&v"(t[3][1])
-          : "v"(b0), "v"(b1));
+      ff_tr_read8(lv[buf], ds, lane, l31, half, t);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        ff_shortx8 vf;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) { vf[x] = t[ks][0][x]; vf[4 + x] = t[ks][1][x]; }
-        oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pb[ks], oacc[ds], 0, 0, 0);
-      }
+      for (int ks = 0; ks < 4; ++ks)
+        oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            ff_cat(t[ks][0], t[ks][1]), pb[ks], oacc[ds], 0, 0, 0);
     }
-
     }  // end relayout+PV (MODE != 2)
     }  // end if (active)
 
@@ -346,9 +220,9 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
     if (have_next) {
 #pragma unroll
       for (int j = 0; j < FF_CHUNKS; ++j) {
-        int e = (tid + j * FF_THREADS) * 8;
-        *reinterpret_cast<ff_shortx8*>((char*)lk[buf ^ 1] + ff_kswz(e * 2)) = kreg[j];
-        *reinterpret_cast<ff_shortx8*>((char*)lv[buf ^ 1] + ff_kswz(e * 2)) = vreg[j];
+        const int e = ff_chunk<FF_THREADS>(j, tid);
+        ff_chunk_store(kreg[j], lk[buf ^ 1], e);
+        ff_chunk_store(vreg[j], lv[buf ^ 1], e);
       }
     }
     __syncthreads();
@@ -356,18 +230,9 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
 
   // ---- epilogue: O[q][d] = acc / l ; lse = m2*ln2 + ln(l) (m2 log2-dom) ----
   float inv_l = (l_run > 0.f) ? 1.0f / l_run : 0.f;
-  unsigned short* og = out + qbase + (int64_t)my_q * FF_D;
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int d = ds * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      og[d] = f32_to_bf16(oacc[ds][r] * inv_l);
-    }
-  if (half == 0) {
-    lse[((int64_t)b * Hq + h) * S + my_q] =
-        m_run * (MODE == 5 ? 1.0f : 0.69314718055994530942f) + __logf(l_run);
-  }
+  ff_store_row(out + c.qbase + (int64_t)my_q * FF_D, oacc, inv_l, half);
+  if (half == 0)
+    lse[c.rbase + my_q] = m_run * (MODE == 5 ? 1.0f : FF_LN2) + __logf(l_run);
 }
 
 // instantiations: the real kernel + ablation variants for profiling

@@ -1,6 +1,8 @@
 // Hardware layout probes and their bindings (decoded by tools/fa_fwd_check.py,
 // tools/permlane_probe.py, tools/tr_probe_check.py).  Included by extension.hip
-// after attention_fwd.hip (FF_* staging helpers) and the host helpers (Binding).
+// after the host helpers (Binding); the device helpers it probes come from
+// fa32_common.h.
+#include "fa32_common.h"
 
 extern "C" __global__ void permlane_probe_kernel(int* out) {
   int x = (int)threadIdx.x;
@@ -38,44 +40,30 @@ extern "C" __global__ void mfma32_probe_kernel(float* out) {
 }
 
 // tr-read addressing probe for the 4x4-group transpose scheme: stage a
-// pattern (value = kv*128 + d) through the SAME swizzled store the kernel
-// uses, then perform the kernel's exact PV reads; host checks lane l elem
+// pattern (value = kv*128 + d) through the kernels' swizzled staging store
+// (ff_chunk_store), then read it back with the kernels' tr-read function
+// (ff_tr_read8); host checks lane l elem
 // e == (ks*16 + half*8 + e)*128 + ds*32 + l31 (tools/tr_probe_check.py).
 extern "C" __global__ void tr_probe_kernel(unsigned short* out) {
-  __shared__ unsigned short lvp[FF_KV * FF_D];
-  int tid = threadIdx.x;
-  for (int i = tid * 8; i < FF_KV * FF_D; i += 64 * 8) {
+  __shared__ unsigned short lvp[64 * FF_D];
+  const int lane = threadIdx.x;  // one wave
+#pragma unroll
+  for (int j = 0; j < FF_STAGE_CHUNKS(64, 64); ++j) {
+    const int e = ff_chunk<64>(j, lane);
     ff_shortx8 vv;
 #pragma unroll
-    for (int x = 0; x < 8; ++x) vv[x] = (short)(i + x);
-    *reinterpret_cast<ff_shortx8*>((char*)lvp + ff_kswz(i * 2)) = vv;
+    for (int x = 0; x < 8; ++x) vv[x] = (short)(e + x);
+    ff_chunk_store(vv, lvp, e);
   }
   __syncthreads();
-  int lane = tid & 63;
-  int l31 = lane & 31;
-  int half = lane >> 5;
+#pragma unroll
   for (int ds = 0; ds < 4; ++ds) {
-    const int col2 = (ds * 32 + (l31 & 16) + (lane & 3) * 4) * 2;
-    const int row0 = half * 8 + ((lane & 15) >> 2);
-    const int a0 = (row0 * 256 + col2) ^ ((row0 & 7) << 4);
-    const int row1 = row0 + 4;
-    const int a1 = (row1 * 256 + col2) ^ ((row1 & 7) << 4);
-    ff_lds_p b0 = (ff_lds_p)((const char*)lvp + a0);
-    ff_lds_p b1 = (ff_lds_p)((const char*)lvp + a1);
-    ff_shortx4 t0, t1;
+    ff_shortx4 t[4][2];
+    ff_tr_read8(lvp, ds, lane, lane & 31, lane >> 5, t);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      switch (ks) {
-        case 0: asm volatile("ds_read_b64_tr_b16 %0, %2 offset:0\n\tds_read_b64_tr_b16 %1, %3 offset:0" : "=v"(t0), "=v"(t1) : "v"(b0), "v"(b1)); break;
-        case 1: asm volatile("ds_read_b64_tr_b16 %0, %2 offset:4096\n\tds_read_b64_tr_b16 %1, %3 offset:4096" : "=v"(t0), "=v"(t1) : "v"(b0), "v"(b1)); break;
-        case 2: asm volatile("ds_read_b64_tr_b16 %0, %2 offset:8192\n\tds_read_b64_tr_b16 %1, %3 offset:8192" : "=v"(t0), "=v"(t1) : "v"(b0), "v"(b1)); break;
-        default: asm volatile("ds_read_b64_tr_b16 %0, %2 offset:12288\n\tds_read_b64_tr_b16 %1, %3 offset:12288" : "=v"(t0), "=v"(t1) : "v"(b0), "v"(b1)); break;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t0), "+v"(t1));
-      unsigned short* o = out + ((ds * 4 + ks) * 64 + lane) * 8;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) { o[x] = (unsigned short)t0[x]; o[4 + x] = (unsigned short)t1[x]; }
-    }
+    for (int ks = 0; ks < 4; ++ks)
+      *reinterpret_cast<ff_shortx8*>(out + ((ds * 4 + ks) * 64 + lane) * 8) =
+          ff_cat(t[ks][0], t[ks][1]);
   }
 }
 
