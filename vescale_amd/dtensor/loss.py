@@ -183,6 +183,11 @@ def dispatcher_default(dispatcher, op, args, kwargs):
 
 @contextlib.contextmanager
 def loss_parallel():
+    """Class-sharded F.cross_entropy on DTensor logits by hooking
+    aten._log_softmax / nll_loss: the log-probs are materialised by
+    construction.  The fused form, which never holds an fp32 [N, V/w]
+    temporary and runs HIP kernels on a bf16 shard, is
+    ops.vocab_parallel_cross_entropy."""
     d = get_dispatcher()
     installed = {
         aten._log_softmax.default: _handler_log_softmax,

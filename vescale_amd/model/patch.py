@@ -2,7 +2,8 @@
 
 Parity: legacy/vescale/model/patch/vp_embedding.py:38 (range mask +
 partial + allreduce) and vp_cross_entropy.py:43-149 (local max ->
-allreduce-max -> masked gather -> allreduce-sum log-sum-exp), as opt-in
+allreduce-max -> masked gather -> allreduce-sum log-sum-exp; here the fused
+ops.vocab_parallel_cross_entropy: two all-reduces, HIP kernels), as opt-in
 module-level rewrites for models whose embedding/classifier weights are
 vocab-sharded Shard(0).
 """
@@ -53,40 +54,18 @@ class VocabParallelEmbedding(nn.Module):
         return out
 
 
-class _VocabParallelCE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits_local, target, start, vocab_total, mesh, mesh_dim):
-        # logits_local: [N, V/w] raw logits shard
-        mx = logits_local.amax(dim=-1, keepdim=True)
-        cc.mesh_all_reduce(mx, mesh, "max", mesh_dim)
-        x = (logits_local - mx).float()
-        ex = x.exp()
-        s = ex.sum(dim=-1, keepdim=True)
-        cc.mesh_all_reduce(s, mesh, "sum", mesh_dim)
-        logz = s.log()
-        n = logits_local.shape[-1]
-        inrange = (target >= start) & (target < start + n)
-        shifted = (target - start).clamp(0, max(0, n - 1))
-        picked = x.gather(-1, shifted.unsqueeze(-1)).squeeze(-1)
-        picked = torch.where(inrange, picked, torch.zeros_like(picked))
-        t = picked.clone()
-        cc.mesh_all_reduce(t, mesh, "sum", mesh_dim)
-        loss = (logz.squeeze(-1) - t)
-        ctx.save_for_backward(ex, s, shifted, inrange)
-        ctx.meta = (mesh, mesh_dim)
-        return loss
+def _vocab_parallel_ce(logits_local, target, start, vocab_total, mesh, mesh_dim):
+    """Per-token loss over a [..., V/w] raw logits shard: the fused
+    vocab-parallel CE of ops (two all-reduces over the mesh dim, none in
+    backward; HIP kernels when the shard is bf16 on the GPU)."""
+    from ..ops import vocab_parallel_cross_entropy
 
-    @staticmethod
-    def backward(ctx, grad_out):
-        ex, s, shifted, inrange = ctx.saved_tensors
-        softmax = ex / s
-        g = grad_out.unsqueeze(-1)
-        dx = softmax * g
-        sub = torch.where(
-            inrange, g.squeeze(-1), torch.zeros_like(g.squeeze(-1))
-        )
-        dx.scatter_add_(-1, shifted.unsqueeze(-1), -sub.unsqueeze(-1))
-        return dx.to(ex.dtype), None, None, None, None, None
+    group = mesh.get_group(mesh_dim) if mesh.size(mesh_dim) > 1 else None
+    n = logits_local.shape[-1]
+    loss = vocab_parallel_cross_entropy(
+        logits_local.reshape(-1, n), target.reshape(-1), start, vocab_total,
+        group=group, ignore_index=-100, reduction="none")
+    return loss.reshape(target.shape)
 
 
 class VocabParallelCrossEntropy(nn.Module):
@@ -111,7 +90,8 @@ class VocabParallelCrossEntropy(nn.Module):
             r = self.mesh.get_local_rank(md)
             start = Shard.chunk_offset(vocab, w, r)
             local = logits._local_tensor
-            loss = _VocabParallelCE.apply(local, target if not isinstance(target, DTensor) else target.to_local(), start, vocab, self.mesh, md)
+            tgt = target.to_local() if isinstance(target, DTensor) else target
+            loss = _vocab_parallel_ce(local, tgt, start, vocab, self.mesh, md)
             return loss
         # dense fallback
         import torch.nn.functional as F

@@ -22,11 +22,12 @@ from ..ops import (
     flash_attention_causal,
     fused_add_rmsnorm,
     fused_cross_entropy,
+    vocab_parallel_cross_entropy,
     rmsnorm,
     rope_qkv,
     swiglu_packed,
 )
-from .llama_tp import TPContext, copy_to_tp, reduce_from_tp
+from .llama_tp import TPContext, copy_to_tp, gather_last_dim, reduce_from_tp
 
 
 class VLinear(nn.Linear):
@@ -50,6 +51,9 @@ class LlamaConfig:
     rope_theta: float = 500000.0
     norm_eps: float = 1e-5
     tie_embeddings: bool = False
+    # TP only: shard the LM head by vocab rows and fuse the class-sharded
+    # loss (ops.vocab_parallel_cross_entropy); the embedding stays replicated
+    vocab_parallel_head: bool = False
 
     @property
     def head_dim(self) -> int:
@@ -188,7 +192,21 @@ class LlamaModel(nn.Module):
             TransformerBlock(cfg, self.tp) for _ in range(cfg.n_layers)
         )
         self.norm = RMSNorm(cfg.dim, cfg.norm_eps)
-        self.output = VLinear(cfg.dim, cfg.vocab_size, bias=False)
+        self.vp_head = cfg.vocab_parallel_head and self.tp.world > 1
+        if self.vp_head:
+            w, r = self.tp.world, self.tp.rank
+            assert cfg.vocab_size % w == 0, (
+                f"vocab_parallel_head: vocab_size = {cfg.vocab_size} is not "
+                f"divisible by the TP world size {w}")
+            assert not cfg.tie_embeddings, (
+                "vocab_parallel_head shards the LM head, the embedding stays "
+                "replicated: the two cannot share one weight")
+            vl = cfg.vocab_size // w
+            # rows [r * V/w, (r + 1) * V/w) of the head
+            self.output = VLinear(cfg.dim, vl, bias=False)
+            self.output.weight._tp_shard = (0, cfg.vocab_size, [(0, vl, r * vl)])
+        else:
+            self.output = VLinear(cfg.dim, cfg.vocab_size, bias=False)
         if cfg.tie_embeddings:
             self.output.weight = self.tok_embeddings.weight
         self.register_buffer(
@@ -228,6 +246,8 @@ class LlamaModel(nn.Module):
             None if delta is None else h,
             self.norm.weight, self.norm.eps,
         )
+        if self.vp_head:
+            return self._vp_head_forward(h, targets, ignore_index)
         logits = self.output(h)
         if targets is None:
             return logits
@@ -235,3 +255,16 @@ class LlamaModel(nn.Module):
             logits.reshape(-1, self.cfg.vocab_size), targets.reshape(-1), ignore_index
         )
         return loss
+
+    def _vp_head_forward(self, h, targets, ignore_index):
+        """Vocab-parallel head: every TP rank multiplies by its V/w rows and
+        the loss is combined from per-rank partials; [B, S, V] logits exist
+        only when the caller asks for them (no targets)."""
+        tp, vl = self.tp, self.output.weight.shape[0]
+        local = self.output(copy_to_tp(h, tp))  # [B, S, V/w]
+        if targets is None:
+            return gather_last_dim(local, tp.group)
+        return vocab_parallel_cross_entropy(
+            local.reshape(-1, vl), targets.reshape(-1), tp.rank * vl,
+            self.cfg.vocab_size, group=tp.group, ignore_index=ignore_index,
+        )

@@ -40,6 +40,9 @@ from .functional import (  # noqa: E402,F401
     flash_attention,
     flash_attention_causal,
     fused_cross_entropy,
+    vocab_parallel_cross_entropy,
+    vp_ce_partials,
+    vp_ce_grad,
     fused_add_rmsnorm,
     rmsnorm,
     rope_apply,

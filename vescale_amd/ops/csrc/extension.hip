@@ -328,26 +328,53 @@ at::Tensor swiglu_packed_bwd(at::Tensor dy, at::Tensor gu) {
 // ------------------------------ Cross entropy ------------------------------
 // Target VALUES are not read here (that would need a device sync): every
 // target inside [0, vocab) or equal to ignore_index is the caller's duty.
+//
+// vocab_total == -1 (the default) is the dense pair.  vocab_total >= 0 is the
+// vocab-parallel pair: logits holds columns [vocab_start, vocab_start + n) of
+// a vocab_total-class row and targets are global ids of ANY value (the
+// kernels compare, they never index with an unchecked target).
+
+// The column range of a vocab-parallel call must lie inside the vocabulary.
+void ce_vp_check(const Binding& b, int64_t n, int64_t vocab_start, int64_t vocab_total) {
+  TORCH_CHECK(vocab_total >= -1, b.fn, ": vocab_total = ", vocab_total,
+              " must be >= 0, or -1 for the dense kernel");
+  TORCH_CHECK(vocab_start >= 0, b.fn, ": vocab_start = ", vocab_start, " must be >= 0");
+  TORCH_CHECK(vocab_total == -1 ? vocab_start == 0 : vocab_start <= vocab_total - n, b.fn,
+              ": vocab_start + n = ", vocab_start, " + ", n,
+              " is past vocab_total = ", vocab_total);
+}
+
+// dense: {loss, lse}; vocab-parallel: {picked, lse_local}
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target,
-                               int64_t ignore_index) {
+                               int64_t ignore_index, int64_t vocab_start,
+                               int64_t vocab_total) {
   Binding b("ce_fwd", "logits", logits);
   int vocab = (int)b.last_dim("vocab (logits.size(-1))", logits, 8);
+  ce_vp_check(b, vocab, vocab_start, vocab_total);
   int64_t rows = logits.numel() / vocab;
   b.arg("logits", logits, BF16);
   b.arg("target", target, I64, Shape::of_numel(rows));
   auto loss = at::empty({rows}, logits.options().dtype(F32));
   auto lse = at::empty({rows}, logits.options().dtype(F32));
   if (rows == 0) return {loss, lse};
-  b.launch(ce_fwd_bf16, (int)std::min<int64_t>(rows, 2048), 256, bf16(logits),
-           target.data_ptr<int64_t>(), loss.data_ptr<float>(), lse.data_ptr<float>(),
-           rows, vocab, ignore_index);
+  int grid = (int)std::min<int64_t>(rows, 2048);
+  if (vocab_total < 0)
+    b.launch(ce_fwd_bf16, grid, 256, bf16(logits), target.data_ptr<int64_t>(),
+             loss.data_ptr<float>(), lse.data_ptr<float>(), rows, vocab, ignore_index);
+  else
+    b.launch(ce_vp_fwd_bf16, grid, 256, bf16(logits), target.data_ptr<int64_t>(),
+             loss.data_ptr<float>(), lse.data_ptr<float>(), rows, vocab, vocab_start,
+             ignore_index);
   return {loss, lse};
 }
 
+// lse: the row's log-sum-exp over the WHOLE vocabulary in either form
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
-                  at::Tensor dloss, int64_t ignore_index, bool inplace) {
+                  at::Tensor dloss, int64_t ignore_index, bool inplace,
+                  int64_t vocab_start, int64_t vocab_total) {
   Binding b("ce_bwd", "logits", logits);
   int vocab = (int)b.last_dim("vocab (logits.size(-1))", logits, 8);
+  ce_vp_check(b, vocab, vocab_start, vocab_total);
   int64_t rows = logits.numel() / vocab;
   b.arg("logits", logits, BF16);
   b.arg("target", target, I64, Shape::of_numel(rows));
@@ -355,9 +382,15 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
   b.arg("dloss", dloss, F32, {rows});
   auto dlogits = inplace ? logits : at::empty_like(logits);
   if (rows == 0) return dlogits;
-  b.launch(ce_bwd_bf16, (int)std::min<int64_t>(rows, 2048), 256, bf16(logits),
-           bf16_mut(dlogits), target.data_ptr<int64_t>(), lse.data_ptr<float>(),
-           dloss.data_ptr<float>(), rows, vocab, ignore_index);
+  int grid = (int)std::min<int64_t>(rows, 2048);
+  if (vocab_total < 0)
+    b.launch(ce_bwd_bf16, grid, 256, bf16(logits), bf16_mut(dlogits),
+             target.data_ptr<int64_t>(), lse.data_ptr<float>(), dloss.data_ptr<float>(),
+             rows, vocab, ignore_index);
+  else
+    b.launch(ce_vp_bwd_bf16, grid, 256, bf16(logits), bf16_mut(dlogits),
+             target.data_ptr<int64_t>(), lse.data_ptr<float>(), dloss.data_ptr<float>(),
+             rows, vocab, vocab_start, ignore_index);
   return dlogits;
 }
 
@@ -742,8 +775,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("swiglu_packed_fwd", &swiglu_packed_fwd);
   m.def("swiglu_packed_bwd", &swiglu_packed_bwd);
-  m.def("ce_fwd", &ce_fwd);
-  m.def("ce_bwd", &ce_bwd);
+  m.def("ce_fwd", &ce_fwd, pybind11::arg("logits"), pybind11::arg("target"),
+        pybind11::arg("ignore_index"), pybind11::arg("vocab_start") = 0,
+        pybind11::arg("vocab_total") = -1);
+  m.def("ce_bwd", &ce_bwd, pybind11::arg("logits"), pybind11::arg("target"),
+        pybind11::arg("lse"), pybind11::arg("dloss"), pybind11::arg("ignore_index"),
+        pybind11::arg("inplace"), pybind11::arg("vocab_start") = 0,
+        pybind11::arg("vocab_total") = -1);
   m.def("adamw_step", &adamw_step);
   m.def("l2norm_sq", &l2norm_sq);
   m.def("scale_", &scale_);

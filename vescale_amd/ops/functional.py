@@ -368,6 +368,152 @@ def fused_cross_entropy(
 
 
 # ---------------------------------------------------------------------------
+# Vocab-parallel cross-entropy: every rank holds columns
+# [vocab_start, vocab_start + n) of the logits (ce_vp_fwd_bf16 /
+# ce_vp_bwd_bf16 in ops/csrc/cross_entropy.hip).
+# ---------------------------------------------------------------------------
+def _vp_hip(logits_local: torch.Tensor, *others) -> bool:
+    return (
+        logits_local.dtype == torch.bfloat16
+        and logits_local.shape[-1] > 0
+        and logits_local.shape[-1] % 8 == 0
+        and _use_hip(logits_local, *others)
+    )
+
+
+def _vp_hit(target, vocab_start, n, ignore_index):
+    """Rows whose target is a column of this shard, and that column."""
+    hit = (target != ignore_index) & (target >= vocab_start) & (target < vocab_start + n)
+    return hit, torch.where(hit, target - vocab_start, torch.zeros_like(target))
+
+
+def _vp_check(logits_local, target, vocab_start, vocab_total):
+    n = logits_local.shape[-1]
+    if logits_local.dim() != 2 or target.shape != logits_local.shape[:1]:
+        raise ValueError(
+            f"vocab-parallel CE takes logits_local [N, n] and target [N], got "
+            f"{tuple(logits_local.shape)} and {tuple(target.shape)}")
+    if vocab_start < 0 or vocab_start + n > vocab_total:
+        raise ValueError(
+            f"shard columns [{vocab_start}, {vocab_start + n}) are not inside "
+            f"the vocabulary [0, {vocab_total})")
+
+
+@torch.no_grad()
+def vp_ce_partials(logits_local, target, vocab_start: int, vocab_total: int,
+                   ignore_index: int = -100):
+    """One shard's share of the cross-entropy: (picked, lse_local), fp32 [N].
+
+    lse_local is the log-sum-exp over the shard's n columns.  picked is the
+    target's raw logit where the target is not ignore_index and lies in
+    [vocab_start, vocab_start + n), else exactly 0; a target outside
+    [0, vocab_total) is in no shard.  HIP for bf16 on the GPU with
+    n % 8 == 0, the fp32 torch reference otherwise."""
+    _vp_check(logits_local, target, vocab_start, vocab_total)
+    if _vp_hip(logits_local, target):
+        picked, lse_local = _ext().ce_fwd(
+            logits_local.contiguous(), target.contiguous(), ignore_index,
+            vocab_start=vocab_start, vocab_total=vocab_total)
+        return picked, lse_local
+    xf = logits_local.to(torch.promote_types(logits_local.dtype, torch.float32))
+    hit, col = _vp_hit(target, vocab_start, xf.shape[-1], ignore_index)
+    xt = xf.gather(-1, col.unsqueeze(-1)).squeeze(-1)
+    return torch.where(hit, xt, torch.zeros_like(xt)), torch.logsumexp(xf, dim=-1)
+
+
+@torch.no_grad()
+def vp_ce_grad(logits_local, target, lse, drow, vocab_start: int, vocab_total: int,
+               ignore_index: int = -100, inplace: bool = False):
+    """dlogits[r, c] = drow[r] * (exp(x[r, c] - lse[r]) - [c + vocab_start ==
+    target[r]]) in logits_local's dtype; lse is the GLOBAL log-sum-exp and
+    drow counts as 0 on ignored rows.  inplace overwrites logits_local (HIP
+    path: no second [N, n] buffer)."""
+    _vp_check(logits_local, target, vocab_start, vocab_total)
+    if _vp_hip(logits_local, target, lse, drow):
+        lg = logits_local.contiguous()
+        out = _ext().ce_bwd(
+            lg, target.contiguous(), lse.float().contiguous(),
+            drow.float().contiguous(), ignore_index, inplace,
+            vocab_start=vocab_start, vocab_total=vocab_total)
+        if inplace and lg is not logits_local:
+            logits_local.copy_(out)
+            return logits_local
+        return out
+    xf = logits_local.to(torch.promote_types(logits_local.dtype, torch.float32))
+    hit, col = _vp_hit(target, vocab_start, xf.shape[-1], ignore_index)
+    p = torch.exp(xf - lse.to(xf.dtype).unsqueeze(-1))
+    p.scatter_add_(-1, col.unsqueeze(-1), -hit.to(p.dtype).unsqueeze(-1))
+    scale = torch.where(target != ignore_index, drow.to(p.dtype), torch.zeros_like(drow, dtype=p.dtype))
+    d = (p * scale.unsqueeze(-1)).to(logits_local.dtype)
+    if inplace:
+        logits_local.copy_(d)
+        return logits_local
+    return d
+
+
+class _VocabParallelCE(torch.autograd.Function):
+    """One node: partials -> (max, sum) all-reduces -> loss; backward is the
+    gradient kernel alone, no collective."""
+
+    @staticmethod
+    def forward(ctx, logits_local, target, vocab_start, vocab_total, group,
+                ignore_index, reduction):
+        picked, lse_local = vp_ce_partials(
+            logits_local, target, vocab_start, vocab_total, ignore_index)
+        if group is not None and torch.distributed.get_world_size(group) > 1:
+            m = lse_local.clone()
+            torch.distributed.all_reduce(
+                m, op=torch.distributed.ReduceOp.MAX, group=group)
+            # a row that is -inf on every shard keeps exp() finite
+            m = torch.where(m == float("-inf"), torch.zeros_like(m), m)
+            both = torch.stack([torch.exp(lse_local - m), picked])
+            torch.distributed.all_reduce(both, group=group)
+            lse, picked = m + torch.log(both[0]), both[1]
+        else:
+            lse = lse_local
+        valid = target != ignore_index
+        rows = torch.where(valid, lse - picked, torch.zeros_like(lse))
+        n_tok = valid.sum().clamp(min=1)
+        ctx.save_for_backward(logits_local, target, lse, n_tok)
+        ctx.args = (vocab_start, vocab_total, ignore_index, reduction)
+        if reduction == "none":
+            return rows
+        return rows.sum() / n_tok.to(rows.dtype)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits_local, target, lse, n_tok = ctx.saved_tensors
+        vocab_start, vocab_total, ignore_index, reduction = ctx.args
+        if reduction == "none":
+            drow = dloss.to(lse.dtype).contiguous()
+        else:
+            drow = (dloss / n_tok.to(dloss.dtype)).to(lse.dtype).expand(lse.shape[0]).contiguous()
+        d = vp_ce_grad(logits_local, target, lse, drow, vocab_start, vocab_total,
+                       ignore_index)
+        return d, None, None, None, None, None, None
+
+
+def vocab_parallel_cross_entropy(
+    logits_local: torch.Tensor, target: torch.Tensor, vocab_start: int,
+    vocab_total: int, group=None, ignore_index: int = -100,
+    reduction: str = "mean",
+) -> torch.Tensor:
+    """Cross-entropy over class-sharded logits: logits_local [N, n] holds
+    columns [vocab_start, vocab_start + n) of a vocab_total-class row on
+    this rank of `group`, target [N] the global class ids (the same on every
+    rank).  The forward makes two all-reduces over `group`, on fp32 fields of
+    N (max) and 2N (sum) elements; the backward makes none.  reduction:
+    "mean" over the non-ignored targets (count clamped to 1) or "none" (the
+    per-row vector, 0 on ignored rows).  group=None is the one-shard case:
+    with vocab_start=0 and vocab_total=n it is fused_cross_entropy's loss."""
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+    return _VocabParallelCE.apply(
+        logits_local, target, int(vocab_start), int(vocab_total), group,
+        int(ignore_index), reduction)
+
+
+# ---------------------------------------------------------------------------
 # Tuned flash attention: our CDNA4 MFMA forward (ops/csrc/attention_fwd.hip,
 # returns logsumexp) + backward (ops/csrc/attention_bwd2.hip); causal,
 # head_dim 128, GQA, seq % 256 == 0.
