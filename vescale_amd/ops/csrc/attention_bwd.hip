@@ -35,7 +35,7 @@ typedef short fa_shortx8 __attribute__((ext_vector_type(8)));
 extern "C" __global__ void __launch_bounds__(256)
 fa_bwd_preprocess(const unsigned short* __restrict__ dout,
                   const unsigned short* __restrict__ o,
-                  float* __restrict__ delta, int64_t rows) {
+                  float* __restrict__ delta, int64_t rows, int Hq, int S, int bshd) {
   // 16 lanes per row (8 elems each), 16 rows per 256-thread block per
   // iteration; fully coalesced loads, shfl-xor reduce inside each 16-lane
   // group, no barriers — HBM-roofline for this pure-bandwidth pass.
@@ -54,7 +54,16 @@ fa_bwd_preprocess(const unsigned short* __restrict__ dout,
 #pragma unroll
     for (int off = 8; off >= 1; off >>= 1)
       s += __shfl_xor(s, off, 64);
-    if (sub == 0) delta[row] = s;
+    // delta is [B,Hq,S] in both layouts.  bshd: dout and o are [B,S,Hq,D] and
+    // `row` walks them in memory order, row = (b*S + s)*Hq + h (rows fits 31
+    // bits there, the binding checks), so only the 4-byte store is scattered.
+    int64_t drow = row;
+    if (bshd) {
+      const unsigned r = (unsigned)row, bs = r / (unsigned)Hq, h = r - bs * (unsigned)Hq;
+      const unsigned bi = bs / (unsigned)S, sq = bs - bi * (unsigned)S;
+      drow = ((int64_t)bi * Hq + h) * S + sq;
+    }
+    if (sub == 0) delta[drow] = s;
   }
 }
 

@@ -26,7 +26,9 @@
 //     barrier per tile (guide T3/T4 phase overlap, structured form)
 //   - O accumulates in D-layout (col = q), so the online rescale by
 //     exp(m_old - m_new) is a lane-local scalar multiply
-//   - outputs: O [B,H,S,D] bf16 and logsumexp [B,H,S] fp32 (ln), matching
+//   - outputs: O [B,H,S,D] (or, out_bshd, [B,S,H,D] — the layout the
+//     output projection reads, so no transpose copy follows) bf16 and
+//     logsumexp [B,H,S] fp32 (ln), matching
 //     the stock flash convention so EITHER backward (ours or the
 //     library's) can consume it.
 // Capability parity: reference vescale relies on library flash attention;
@@ -46,13 +48,16 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
             const unsigned short* __restrict__ v,
             unsigned short* __restrict__ out,
             float* __restrict__ lse,
-            int B, int Hq, int Hkv, int S, float scale) {
+            int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
   __shared__ unsigned short lk[2][FF_KV * FF_D];  // K, swizzled
   __shared__ unsigned short lv[2][FF_KV * FF_D];  // V, swizzled (same as K)
 
   const ff_ctx c = ff_prologue(Hq, Hkv, S);
   const int tid = c.tid, lane = c.lane, l31 = c.l31, half = c.half;
-  const int qt = c.tile;                             // q macro-tile
+  // q macro-tile, ascending.  (Walking a head's tiles heaviest first, as
+  // fa2_dq does, was measured here too: 3.51 -> 3.42 ms per call, inside this
+  // kernel's own call-to-call spread of 0.08-0.10 ms, so it was not kept.)
+  const int qt = c.tile;
   const int q0 = qt * FF_QTILE + c.wave * FF_QBLK;   // wave's first q row
   const int my_q = q0 + l31;                         // this lane's q row
   const float scale2 = (MODE == 5) ? scale : scale * FF_LOG2E;
@@ -230,7 +235,10 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
 
   // ---- epilogue: O[q][d] = acc / l ; lse = m2*ln2 + ln(l) (m2 log2-dom) ----
   float inv_l = (l_run > 0.f) ? 1.0f / l_run : 0.f;
-  ff_store_row(out + c.qbase + (int64_t)my_q * FF_D, oacc, inv_l, half);
+  // out rows in the caller's layout ([B,Hq,S,D] or [B,S,Hq,D]): a row is 128
+  // contiguous elements in both, only its address differs.
+  const ff_rows orow = ff_o_rows(c, Hq, S, out_bshd);
+  ff_store_row(out + orow.base + (int64_t)my_q * orow.stride, oacc, inv_l, half);
   if (half == 0)
     lse[c.rbase + my_q] = m_run * (MODE == 5 ? 1.0f : FF_LN2) + __logf(l_run);
 }
@@ -239,36 +247,36 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
 extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16(const unsigned short* q, const unsigned short* k,
             const unsigned short* v, unsigned short* out, float* lse,
-            int B, int Hq, int Hkv, int S, float scale) {
-  fa_fwd_t<0>(q, k, v, out, lse, B, Hq, Hkv, S, scale);
+            int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
+  fa_fwd_t<0>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
 extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab1(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
-                int B, int Hq, int Hkv, int S, float scale) {
-  fa_fwd_t<1>(q, k, v, out, lse, B, Hq, Hkv, S, scale);
+                int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
+  fa_fwd_t<1>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
 extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab2(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
-                int B, int Hq, int Hkv, int S, float scale) {
-  fa_fwd_t<2>(q, k, v, out, lse, B, Hq, Hkv, S, scale);
+                int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
+  fa_fwd_t<2>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
 extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab3(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
-                int B, int Hq, int Hkv, int S, float scale) {
-  fa_fwd_t<3>(q, k, v, out, lse, B, Hq, Hkv, S, scale);
+                int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
+  fa_fwd_t<3>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
 extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab4(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
-                int B, int Hq, int Hkv, int S, float scale) {
-  fa_fwd_t<4>(q, k, v, out, lse, B, Hq, Hkv, S, scale);
+                int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
+  fa_fwd_t<4>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
 extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab5(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
-                int B, int Hq, int Hkv, int S, float scale) {
-  fa_fwd_t<5>(q, k, v, out, lse, B, Hq, Hkv, S, scale);
+                int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
+  fa_fwd_t<5>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }

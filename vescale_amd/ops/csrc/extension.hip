@@ -185,7 +185,10 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
   int grid = (int)std::min<int64_t>(rows, 1024);
   // one dw row per block, summed below in a fixed order (deterministic)
   auto dw_part = at::empty({grid, hidden}, x.options().dtype(F32));
-  b.launch(rmsnorm_bwd_bf16, grid, 256, bf16(dy), bf16(x), bf16(w),
+  // the instantiation with just enough 8-element chunks per thread
+  decltype(&rmsnorm_bwd_bf16) kerns[] = {rmsnorm_bwd_it1_bf16, rmsnorm_bwd_it2_bf16,
+                                         rmsnorm_bwd_it3_bf16, rmsnorm_bwd_bf16};
+  b.launch(kerns[(hidden - 1) / 2048], grid, 256, bf16(dy), bf16(x), bf16(w),
            rrms.data_ptr<float>(), bf16(dres), bf16_mut(dx), dw_part.data_ptr<float>(),
            rows, hidden);
   return {dx, dw_part.sum(0)};
@@ -240,6 +243,18 @@ int64_t rope_qkv_check(const Binding& b, const at::Tensor& table, int64_t B, int
   return B * S * (Hq + 2 * Hkv) * (D / 2);
 }
 
+// The 16-byte kernels take D % 16 == 0 with at most 64 units of 16 elements
+// per head (one wave covers a head) and 16-byte aligned tensors; every other
+// call runs the scalar kernels.
+bool rope_qkv_v8(int64_t D, std::initializer_list<const at::Tensor*> ts) {
+  if (D % 16 != 0 || D / 16 > 64) return false;
+  for (const at::Tensor* t : ts)
+    if (reinterpret_cast<uintptr_t>(t->const_data_ptr()) % 16 != 0) return false;
+  return true;
+}
+// one wave per token, 4 tokens per block pass
+int rope_qkv_v8_grid(int64_t tokens) { return grid_for(tokens, 4, 1 << 16); }
+
 std::vector<at::Tensor> rope_qkv_fwd(at::Tensor qkv, at::Tensor table, int64_t B,
                                      int64_t S, int64_t Hq, int64_t Hkv, int64_t D,
                                      int64_t pos_offset) {
@@ -251,7 +266,10 @@ std::vector<at::Tensor> rope_qkv_fwd(at::Tensor qkv, at::Tensor table, int64_t B
   auto q = at::empty({B, Hq, S, D}, opt);
   auto k = at::empty({B, Hkv, S, D}, opt);
   auto v = at::empty({B, Hkv, S, D}, opt);
-  b.launch(rope_qkv_fwd_bf16, grid_for(total, 256), 256, bf16(qkv), bf16_mut(q),
+  if (total == 0) return {q, k, v};
+  const bool v8 = rope_qkv_v8(D, {&qkv, &q, &k, &v, &table});
+  b.launch(v8 ? rope_qkv_fwd_v8_bf16 : rope_qkv_fwd_bf16,
+           v8 ? rope_qkv_v8_grid(B * S) : grid_for(total, 256), 256, bf16(qkv), bf16_mut(q),
            bf16_mut(k), bf16_mut(v), table.data_ptr<float>(), B * S, (int)S, (int)Hq,
            (int)Hkv, (int)D, (int)pos_offset);
   return {q, k, v};
@@ -267,9 +285,12 @@ at::Tensor rope_qkv_bwd(at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor 
   b.arg("dv", dv, BF16, {B, Hkv, S, D});
   b.arg("table", table, F32, {-1, D / 2, 2});
   auto dqkv = at::empty({B, S, (Hq + 2 * Hkv) * D}, dq.options());
-  b.launch(rope_qkv_bwd_bf16, grid_for(total, 256), 256, bf16(dq), bf16(dk), bf16(dv),
-           bf16_mut(dqkv), table.data_ptr<float>(), B * S, (int)S, (int)Hq, (int)Hkv,
-           (int)D, (int)pos_offset);
+  if (total == 0) return dqkv;
+  const bool v8 = rope_qkv_v8(D, {&dq, &dk, &dv, &dqkv, &table});
+  b.launch(v8 ? rope_qkv_bwd_v8_bf16 : rope_qkv_bwd_bf16,
+           v8 ? rope_qkv_v8_grid(B * S) : grid_for(total, 256), 256, bf16(dq), bf16(dk),
+           bf16(dv), bf16_mut(dqkv), table.data_ptr<float>(), B * S, (int)S, (int)Hq,
+           (int)Hkv, (int)D, (int)pos_offset);
   return dqkv;
 }
 
@@ -502,11 +523,12 @@ at::Tensor gemm_tn8(at::Tensor a, at::Tensor b, int64_t mode) {
 // ------------------------------ tuned flash attention (causal, D=128) ------
 struct FaShape { int B, Hq, Hkv, S; };
 
-// q,o,dout: [B,Hq,S,128]; k,v: [B,Hkv,S,128]; lse: [B,Hq,S] f32; S % tile == 0.
-// The forward bindings pass no o/dout/lse.
+// q: [B,Hq,S,128]; k,v: [B,Hkv,S,128]; lse: [B,Hq,S] f32; S % tile == 0.
+// o,dout: [B,Hq,S,128], or with bshd [B,S,Hq,128].  The forward bindings pass
+// no o/dout/lse.
 FaShape fa_check(const Binding& b, int tile, const at::Tensor& q, const at::Tensor& k,
                  const at::Tensor& v, const OptTensor& o = {},
-                 const OptTensor& dout = {}, const OptTensor& lse = {}) {
+                 const OptTensor& dout = {}, const OptTensor& lse = {}, bool bshd = false) {
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4, b.fn, ": q, k must be [B,H,S,128], got q sizes=",
               q.sizes(), " k sizes=", k.sizes());
   int64_t B = q.size(0), Hq = q.size(1), S = q.size(2), Hkv = k.size(1);
@@ -517,27 +539,37 @@ FaShape fa_check(const Binding& b, int tile, const at::Tensor& q, const at::Tens
   b.arg("q", q, BF16, {B, Hq, S, FF_D});
   b.arg("k", k, BF16, {B, Hkv, S, FF_D});
   b.arg("v", v, BF16, {B, Hkv, S, FF_D});
-  b.arg("o", o, BF16, {B, Hq, S, FF_D});
-  b.arg("dout", dout, BF16, {B, Hq, S, FF_D});
+  // the [B,S,Hq,D] kernels index rows and a 256-row tile's elements in int
+  TORCH_CHECK(!bshd || (B * Hq * S <= INT_MAX && Hq * FF_D * 256 <= INT_MAX), b.fn,
+              ": B * Hq * S and Hq * 32768 must fit int in the [B,S,Hq,D] layout");
+  const Shape oshape = bshd ? Shape{B, S, Hq, FF_D} : Shape{B, Hq, S, FF_D};
+  b.arg("o", o, BF16, oshape);
+  b.arg("dout", dout, BF16, oshape);
   b.arg("lse", lse, F32, {B, Hq, S});
   return {(int)B, (int)Hq, (int)Hkv, (int)S};
 }
 static_assert(FA_D == FF_D && FB_D == FF_D, "tuned attention kernels share D");
 
+// out_bshd: o is allocated and written as [B,S,Hq,D]; lse stays [B,Hq,S]
 std::vector<at::Tensor> fa_fwd_impl(const Binding& b, int64_t mode, at::Tensor q,
-                                    at::Tensor k, at::Tensor v, double scale) {
+                                    at::Tensor k, at::Tensor v, double scale,
+                                    bool out_bshd) {
   FaShape s = fa_check(b, FF_QTILE, q, k, v);
-  auto out = at::empty_like(q);
+  TORCH_CHECK(!out_bshd || (int64_t)s.Hq * FF_D <= INT_MAX, b.fn,
+              ": Hq * 128 must fit int in the [B,S,Hq,D] layout");
+  auto out = out_bshd ? at::empty({s.B, s.S, s.Hq, FF_D}, q.options()) : at::empty_like(q);
   auto lse = at::empty({s.B, s.Hq, s.S}, q.options().dtype(F32));
   decltype(&fa_fwd_bf16) kerns[] = {fa_fwd_bf16,     fa_fwd_bf16_ab1, fa_fwd_bf16_ab2,
                                     fa_fwd_bf16_ab3, fa_fwd_bf16_ab4, fa_fwd_bf16_ab5};
   b.launch(kerns[mode], dim3(s.S / FF_QTILE, s.Hq, s.B), FF_THREADS, bf16(q), bf16(k), bf16(v),
-           bf16_mut(out), lse.data_ptr<float>(), s.B, s.Hq, s.Hkv, s.S, (float)scale);
+           bf16_mut(out), lse.data_ptr<float>(), s.B, s.Hq, s.Hkv, s.S, (float)scale,
+           out_bshd ? 1 : 0);
   return {out, lse};
 }
 
-std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale) {
-  return fa_fwd_impl(Binding("fa_fwd", "q", q), 0, q, k, v, scale);
+std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
+                               bool out_bshd) {
+  return fa_fwd_impl(Binding("fa_fwd", "q", q), 0, q, k, v, scale, out_bshd);
 }
 
 std::vector<at::Tensor> fa_fwd_ablate(at::Tensor q, at::Tensor k, at::Tensor v,
@@ -546,16 +578,17 @@ std::vector<at::Tensor> fa_fwd_ablate(at::Tensor q, at::Tensor k, at::Tensor v,
   // mode != 0); see attention_fwd.hip template MODE docs
   TORCH_CHECK(mode >= 0 && mode <= 5, "fa_fwd_ablate: mode = ", mode,
               " must be in 0..5");
-  return fa_fwd_impl(Binding("fa_fwd_ablate", "q", q), mode, q, k, v, scale);
+  return fa_fwd_impl(Binding("fa_fwd_ablate", "q", q), mode, q, k, v, scale, false);
 }
 
-// delta[row] = sum_d dout * o, shared by both tuned backwards
+// delta[b,h,s] = sum_d dout * o, shared by both tuned backwards; bshd: dout
+// and o are [B,S,Hq,D]
 at::Tensor fa_bwd_delta(const Binding& b, const FaShape& s, const at::Tensor& dout,
-                        const at::Tensor& o) {
+                        const at::Tensor& o, bool bshd = false) {
   auto delta = at::empty({s.B, s.Hq, s.S}, o.options().dtype(F32));
   int64_t rows = (int64_t)s.B * s.Hq * s.S;
   b.launch(fa_bwd_preprocess, grid_for(rows, 1, 4096), 256, bf16(dout), bf16(o),
-           delta.data_ptr<float>(), rows);
+           delta.data_ptr<float>(), rows, s.Hq, s.S, bshd ? 1 : 0);
   return delta;
 }
 
@@ -591,17 +624,20 @@ std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Ten
 // ------------------------------ flash-attention backward v2 ---------------
 std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                 at::Tensor dout, at::Tensor lse, double scale,
-                                bool fused_dvdk) {
+                                bool fused_dvdk, bool bshd) {
   // 32x32-MFMA backward (attention_bwd2.hip): preprocess + dq + dv + dk
-  // (+ GQA reduction); lse ln-domain.
+  // (+ GQA reduction); lse ln-domain.  bshd: o and dout are [B,S,Hq,D] (the
+  // split kernels only); dq/dk/dv are [B,H,S,D] either way.
   Binding b("fa_bwd2", "q", q);
-  FaShape s = fa_check(b, FB_TILE, q, k, v, o, dout, lse);
-  auto delta = fa_bwd_delta(b, s, dout, o);
+  TORCH_CHECK(!(bshd && fused_dvdk), "fa_bwd2: the fused dv+dk kernel reads [B,Hq,S,D] ",
+              "only: bshd=True needs fused_dvdk=False");
+  FaShape s = fa_check(b, FB_TILE, q, k, v, o, dout, lse, bshd);
+  auto delta = fa_bwd_delta(b, s, dout, o, bshd);
   auto dq = at::empty_like(q);
   dim3 grid(s.S / FB_TILE, s.Hq, s.B);
   b.launch(fa2_dq_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
            lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), s.B, s.Hq,
-           s.Hkv, s.S, (float)scale);
+           s.Hkv, s.S, (float)scale, bshd ? 1 : 0);
   auto dv_part = at::empty_like(q);
   auto dk_part = at::empty_like(q);
   if (fused_dvdk) {
@@ -614,10 +650,10 @@ std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Te
   } else {
     b.launch(fa2_dv_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(dout),
              lse.data_ptr<float>(), bf16_mut(dv_part), s.B, s.Hq, s.Hkv, s.S,
-             (float)scale);
+             (float)scale, bshd ? 1 : 0);
     b.launch(fa2_dk_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
              lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dk_part), s.B,
-             s.Hq, s.Hkv, s.S, (float)scale);
+             s.Hq, s.Hkv, s.S, (float)scale, bshd ? 1 : 0);
   }
   return {dq, fa_bwd_reduce(b, s, dk_part), fa_bwd_reduce(b, s, dv_part)};
 }
@@ -788,8 +824,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_tn", &gemm_tn, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("variant") = 0);
   m.def("gemm_tn8", &gemm_tn8, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("mode") = 0);
   m.def("fa_bwd", &fa_bwd);
-  m.def("fa_bwd2", &fa_bwd2);
-  m.def("fa_fwd", &fa_fwd);
+  m.def("fa_bwd2", &fa_bwd2, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("o"), pybind11::arg("dout"), pybind11::arg("lse"),
+        pybind11::arg("scale"), pybind11::arg("fused_dvdk"), pybind11::arg("bshd") = false);
+  m.def("fa_fwd", &fa_fwd, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("scale"), pybind11::arg("out_bshd") = false);
   m.def("fa_fwd_ablate", &fa_fwd_ablate);
   m.def("fa_gen_fwd", &fa_gen_fwd, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("causal"),

@@ -109,6 +109,34 @@ DEV void ff_stage(const unsigned short* __restrict__ g, unsigned short* l, int t
   }
 }
 
+// Rows of one head of an o-shaped tensor (o, dout) in either layout: row r of
+// head (b, h) starts at element base + r * stride.  [B,Hq,S,D]: the head's
+// rows are D apart; [B,S,Hq,D]: they are Hq*D apart and the head picks a
+// 128-element column band.  Block-uniform, so it lives in scalar registers.
+struct ff_rows {
+  int64_t base;
+  int stride;
+};
+DEV ff_rows ff_o_rows(const ff_ctx& c, int Hq, int S, int bshd) {
+  ff_rows r;
+  r.stride = bshd ? Hq * FF_D : FF_D;
+  r.base = bshd ? ((int64_t)c.b * S * Hq + c.h) * FF_D : c.qbase;
+  return r;
+}
+
+// ff_stage's strided sibling: the tile's row i starts at g + i * stride
+// (stride = FF_D is ff_stage itself).  LDS image identical to ff_stage's.
+template <int ROWS, int THREADS>
+DEV void ff_stage_rows(const unsigned short* __restrict__ g, int stride, unsigned short* l,
+                       int tid) {
+#pragma unroll
+  for (int j = 0; j < FF_STAGE_CHUNKS(ROWS, THREADS); ++j) {
+    const int e = ff_chunk<THREADS>(j, tid);
+    const int ge = (e / FF_D) * stride + (e % FF_D);
+    ff_chunk_store(ff_chunk_load(g, ge), l, e);
+  }
+}
+
 // A-operand fragment: rows s2*32 + l31 of a swizzled [*x128] LDS tile,
 // k = ks*16 + half*8 + e
 DEV ff_shortx8 ff_afrag(const unsigned short* l, int s2, int ks, int l31, int half) {

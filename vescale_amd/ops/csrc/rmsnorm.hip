@@ -135,8 +135,12 @@ rmsnorm_res_fwd_bf16(const unsigned short* __restrict__ x,
 // stored as row blockIdx.x of the fp32 [gridDim.x, H] partial buffer; the
 // caller reduces the rows (no atomics: fp32 atomicAdd order made dw, and
 // with it the whole train step, differ from run to run).
-extern "C" __global__ void __launch_bounds__(BLOCK)
-rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
+// ITERS = 8-element chunks per thread, ceil(hidden / 2048): a template
+// parameter so that hidden 4096 does not carry the registers of 8192.  Every
+// instantiation does the same operations in the same order on the same
+// threads, so results do not depend on which one runs.
+template <int ITERS>
+DEV void rmsnorm_bwd_t(const unsigned short* __restrict__ dy,
                  const unsigned short* __restrict__ x,
                  const unsigned short* __restrict__ w,
                  const float* __restrict__ rrms_in,
@@ -150,14 +154,13 @@ rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
   // per-thread register cache of the row data: pass 1 reads dy/x/w from
   // global ONCE; pass 2 consumes the registers (hidden <= 8192 at BLOCK
   // 256 -> up to 4 iters x 8 elems live per tensor)
-  const int per_row_iters = (hidden / vec + BLOCK - 1) / BLOCK;
-  float dw_acc[32];
+  float dw_acc[ITERS * 8];
 #pragma unroll
-  for (int j = 0; j < 32; ++j) dw_acc[j] = 0.f;
+  for (int j = 0; j < ITERS * 8; ++j) dw_acc[j] = 0.f;
   // w is row-invariant: load once per thread
-  float wreg[32];
+  float wreg[ITERS * 8];
   #pragma unroll
-  for (int it = 0; it < 4; ++it) {
+  for (int it = 0; it < ITERS; ++it) {
     int i = (it * BLOCK + threadIdx.x) * vec;
     if (i < hidden) {
       short8v wv = *reinterpret_cast<const short8v*>(w + i);
@@ -172,9 +175,9 @@ rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
     unsigned short* dxr = dx + row * hidden;
     float rrms = rrms_in[row];
     float dot = 0.f;
-    float dyreg[32], xreg[32];
+    float dyreg[ITERS * 8], xreg[ITERS * 8];
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < ITERS; ++it) {
       int i = (it * BLOCK + threadIdx.x) * vec;
       if (i < hidden) {
         short8v dv = *reinterpret_cast<const short8v*>(dyr + i);
@@ -192,7 +195,7 @@ rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
     float tdot = block_reduce_sum<BLOCK>(dot, lds);
     float coef = tdot * rrms * rrms * rrms / (float)hidden;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < ITERS; ++it) {
       int i = (it * BLOCK + threadIdx.x) * vec;
       if (i < hidden) {
         short8v o;
@@ -216,7 +219,7 @@ rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
   // fixed order, so dw is bitwise repeatable run to run)
   float* dwr = dw_part + (int64_t)blockIdx.x * hidden;
   #pragma unroll
-  for (int it = 0; it < 4; ++it) {
+  for (int it = 0; it < ITERS; ++it) {
     int i = (it * BLOCK + threadIdx.x) * vec;
     if (i < hidden) {
 #pragma unroll
@@ -224,3 +227,16 @@ rmsnorm_bwd_bf16(const unsigned short* __restrict__ dy,
     }
   }
 }
+
+#define RMSNORM_BWD(NAME, ITERS)                                                \
+  extern "C" __global__ void __launch_bounds__(BLOCK) NAME(                     \
+      const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x, \
+      const unsigned short* __restrict__ w, const float* __restrict__ rrms_in,  \
+      const unsigned short* __restrict__ dres, unsigned short* __restrict__ dx, \
+      float* __restrict__ dw_part, int64_t n_rows, int hidden) {                \
+    rmsnorm_bwd_t<ITERS>(dy, x, w, rrms_in, dres, dx, dw_part, n_rows, hidden); \
+  }
+RMSNORM_BWD(rmsnorm_bwd_bf16, 4)      // 6144 < hidden <= 8192 (and any smaller)
+RMSNORM_BWD(rmsnorm_bwd_it3_bf16, 3)  // hidden <= 6144
+RMSNORM_BWD(rmsnorm_bwd_it2_bf16, 2)  // hidden <= 4096
+RMSNORM_BWD(rmsnorm_bwd_it1_bf16, 1)  // hidden <= 2048

@@ -523,34 +523,58 @@ class _FlashAttention(torch.autograd.Function):
     (attention_fwd.hip, ~565 TF at the Llama-8B shape vs the stock AOTriton
     forward's ~477 TF) + fa_bwd2 (attention_bwd2.hip, ~18.7 ms vs the
     library backward's ~20.9 ms at that shape).  Set VESCALE_FA=aten to
-    fall back to the torch/AOTriton kernels."""
+    fall back to the torch/AOTriton kernels.
+
+    o is produced, saved and differentiated as [B, S, H, D]: the forward
+    returns its [B, H, S, D]-shaped view and the backward reads dout in the
+    same layout, which removed the two transpose copies per layer (0.134 ms
+    each at the Llama-8B bench shape, 64 launches per step) around the
+    output projection.  fa_fwd and fa2_dq are as fast as before; fa2_dv and
+    fa2_dk stage dO rows that are now 8 KiB apart and cost 0.13-0.19 ms more
+    per layer between them, so the net is about -0.1 ms per layer
+    (profiles/streaming_kernels_r3.txt)."""
 
     @staticmethod
     def forward(ctx, q, k, v, scale):
-        # q,k,v: [B, H, S, D] contiguous bf16
-        out, lse = _ext().fa_fwd(q, k, v, scale)
+        # q,k,v: [B, H, S, D] contiguous bf16.  The kernel writes o as
+        # [B, S, H, D], the layout the output projection reads; callers get
+        # the [B, H, S, D]-shaped view of it.
+        out, lse = _ext().fa_fwd(q, k, v, scale, out_bshd=True)
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.scale = scale
-        return out
+        return out.transpose(1, 2)
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
         # default OFF: the fused dv+dk kernel is numerically exact but
         # measured SLOWER (whole bwd 17.9 ms vs 11.2 ms at B4 H32/8 S8192,
-        # gpurun_out/fa_fused_check.log) — its 2-accumulator register set
+        # profiles/fa_fused_dvdk_ab_r2.log) — its 2-accumulator register set
         # only fits at 1 wave/SIMD (4-wave blocks), and the lost latency
-        # hiding outweighs the deduplicated ST GEMM + staging.  Kept for A/B.
+        # hiding outweighs the deduplicated ST GEMM + staging.  Kept for A/B;
+        # it reads [B, H, S, D] only.
         fused = os.environ.get("VESCALE_FA_FUSED_DVDK", "0") == "1"
-        dq, dk, dv = _ext().fa_bwd2(
-            q, k, v, out, dout.contiguous(), lse, ctx.scale, fused
-        )
+        if fused:
+            dq, dk, dv = _ext().fa_bwd2(
+                q, k, v, out.transpose(1, 2).contiguous(), dout.contiguous(), lse,
+                ctx.scale, True)
+            return dq, dk, dv, None
+        # the gradient of the [B, H, S, D] view of a [B, S, H*D] consumer is
+        # contiguous once transposed back: no copy on the model's path
+        dout = dout.transpose(1, 2)
+        if not dout.is_contiguous():
+            dout = dout.contiguous()
+        dq, dk, dv = _ext().fa_bwd2(q, k, v, out, dout, lse, ctx.scale, False, bshd=True)
         return dq, dk, dv, None
 
 
 def flash_attention_causal(q, k, v):
     """Causal flash attention, [B,H,S,D] bf16; GQA via Hkv < Hq.  Falls back
-    to torch SDPA off-GPU / without the extension loudly on GPU."""
+    to torch SDPA off-GPU / without the extension loudly on GPU.
+
+    On the HIP path the result is a [B,H,S,D]-shaped VIEW of a contiguous
+    [B,S,H,D] tensor (not contiguous itself): o.transpose(1, 2).reshape(B, S,
+    H*D), what an output projection wants, is a view too."""
     import math
 
     scale = 1.0 / math.sqrt(q.shape[-1])
