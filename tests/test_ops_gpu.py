@@ -436,9 +436,8 @@ def test_gemm8_tn():
 
 @requires_gpu
 def test_flash_attention_bwd_kernel():
-    """Direct test of our fa_bwd MFMA kernel (attention_bwd.hip) — kept as
-    an alternative backward (slower than the library's today, see
-    NOTES_ROUND2.md) — vs SDPA autograd grads."""
+    """The 16x16-MFMA backward (fa_gen_bwd, attention_gen.hip) fed with the
+    tuned forward's o and lse (fa_fwd) — vs SDPA autograd grads."""
     import math
 
     import torch.nn.functional as F
@@ -454,7 +453,7 @@ def test_flash_attention_bwd_kernel():
     dy = torch.randn(B, Hq, S, D, device="cuda", dtype=torch.bfloat16)
     sc = 1.0 / math.sqrt(D)
     o, lse = C.fa_fwd(q.detach(), k.detach(), v.detach(), sc)
-    dq, dk, dv = C.fa_bwd(q.detach(), k.detach(), v.detach(), o, dy, lse, sc)
+    dq, dk, dv = C.fa_gen_bwd(q.detach(), k.detach(), v.detach(), o, dy, lse, None, sc, True, 0)
     ref = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=True)
     ref.backward(dy)
     assert torch.allclose(dq.float(), q.grad.float(), atol=6e-2, rtol=8e-2)

@@ -1,4 +1,4 @@
-"""fa_bwd2 refcheck vs autograd + timing vs library/old bwd (GPU)."""
+"""fa_bwd2 refcheck vs autograd + timing vs the library and general backwards (GPU)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import math, time, torch
@@ -49,8 +49,8 @@ t2 = bench(lambda: C.fa_bwd2(q, k, v, o, dy, lse, sc, True))
 print(f"fa_bwd2 fused dvdk: {t2*1e3:.2f} ms")
 t2u = bench(lambda: C.fa_bwd2(q, k, v, o, dy, lse, sc, False))
 print(f"fa_bwd2 split dvdk: {t2u*1e3:.2f} ms")
-t1 = bench(lambda: C.fa_bwd(q, k, v, o, dy, lse, sc))
-print(f"fa_bwd (old): {t1*1e3:.2f} ms")
+t1 = bench(lambda: C.fa_gen_bwd(q, k, v, o, dy, lse, None, sc, True, 0))
+print(f"fa_gen_bwd (general 16x16 kernels): {t1*1e3:.2f} ms")
 # library backward via autograd on aten path
 philox = torch.zeros((), device="cuda", dtype=torch.int64)
 def lib():

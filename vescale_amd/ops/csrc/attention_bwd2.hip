@@ -1,7 +1,7 @@
 // Flash-attention BACKWARD v2 — CDNA4 MFMA 32x32x16, causal, GQA, D=128.
 //
-// Replaces the 16x16-MFMA attention_bwd.hip hot kernels with the patterns
-// proven out in attention_fwd.hip, through the same fa32_common.h helpers
+// The tuned backward: the patterns proven out in attention_fwd.hip, through
+// the same fa32_common.h helpers
 // (ff_stage swizzled staging, ff_relayout permlane relayout, ff_tr_read8
 // 4x4-group ds_read_b64_tr_b16 transpose reads — all probe-verified on
 // hardware, tools/tr_probe_check.py).  ff_tr_read8 reads only the low 4 bits
@@ -27,8 +27,8 @@
 //              dKacc[d][kv] += mfma(A=Q^T tr-frags, B=relayout(dS))
 //            Epilogue dK[kv][d] = scale * acc.
 //
-// dV/dK write per-Hq partials; the existing fa_bwd_reduce_gqa kernel sums
-// the GQA groups, and fa_bwd_preprocess provides delta = rowsum(dO*O).
+// fa_bwd_preprocess provides delta = rowsum(dO*O); dV/dK write per-Hq
+// partials and fa_bwd_reduce_gqa sums the GQA groups.
 //
 // Reference parity: the reference framework uses the stock flash kernels;
 // this replaces the train step's heaviest kernel (the library backward is
@@ -41,6 +41,76 @@
 #define FB_TILE (FB_OWN * FB_WAVES)  // 256 own-rows per block
 #define FB_OTH 64             // other-side tile (kv for dq; q for dv/dk)
 #define FB_THREADS (FB_WAVES * 64)
+
+// ---------------------------------------------------------------------------
+// delta = rowsum(dO * O)   [B*H*S rows of D elems]
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(256)
+fa_bwd_preprocess(const unsigned short* __restrict__ dout,
+                  const unsigned short* __restrict__ o,
+                  float* __restrict__ delta, int64_t rows, int Hq, int S, int bshd) {
+  // 16 lanes per row (8 elems each), 16 rows per 256-thread block per
+  // iteration; fully coalesced loads, shfl-xor reduce inside each 16-lane
+  // group, no barriers — HBM-roofline for this pure-bandwidth pass.
+  const int sub = threadIdx.x & 15;         // lane within row
+  int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int64_t stride = (int64_t)gridDim.x * 16;
+  for (; row < rows; row += stride) {
+    const unsigned short* pd = dout + row * FB_D + sub * 8;
+    const unsigned short* po = o + row * FB_D + sub * 8;
+    ff_shortx8 a = *reinterpret_cast<const ff_shortx8*>(pd);
+    ff_shortx8 b = *reinterpret_cast<const ff_shortx8*>(po);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      s += bf16_to_f32((unsigned short)a[j]) * bf16_to_f32((unsigned short)b[j]);
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1)
+      s += __shfl_xor(s, off, 64);
+    // delta is [B,Hq,S] in both layouts.  bshd: dout and o are [B,S,Hq,D] and
+    // `row` walks them in memory order, row = (b*S + s)*Hq + h (rows fits 31
+    // bits there, the binding checks), so only the 4-byte store is scattered.
+    int64_t drow = row;
+    if (bshd) {
+      const unsigned r = (unsigned)row, bs = r / (unsigned)Hq, h = r - bs * (unsigned)Hq;
+      const unsigned bi = bs / (unsigned)S, sq = bs - bi * (unsigned)S;
+      drow = ((int64_t)bi * Hq + h) * S + sq;
+    }
+    if (sub == 0) delta[drow] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// reduce GQA partials: dk[b,hkv,s,d] = sum over group of dk_part[b,h,s,d]
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(256)
+fa_bwd_reduce_gqa(const unsigned short* __restrict__ part,  // [B,Hq,S,D]
+                  unsigned short* __restrict__ out,         // [B,Hkv,S,D]
+                  int B, int Hq, int Hkv, int64_t SD) {
+  int group = Hq / Hkv;
+  int64_t total = (int64_t)B * Hkv * SD;
+  int64_t i0 = (int64_t)(blockIdx.x * 256 + threadIdx.x) * 8;
+  int64_t stride = (int64_t)gridDim.x * 256 * 8;
+  for (int64_t i = i0; i < total; i += stride) {
+    int64_t bh = i / SD;
+    int64_t off = i % SD;
+    int64_t b = bh / Hkv;
+    int64_t hk = bh % Hkv;
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll 4
+    for (int g = 0; g < group; ++g) {
+      const unsigned short* p =
+          part + ((b * Hq + hk * group + g) * SD) + off;
+      ff_shortx8 v = *reinterpret_cast<const ff_shortx8*>(p);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += bf16_to_f32((unsigned short)v[j]);
+    }
+    ff_shortx8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (short)f32_to_bf16(acc[j]);
+    *reinterpret_cast<ff_shortx8*>(out + i) = o;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // fa2_dq: dQ = scale * K^T-contract(dS'); grid (S/256, Hq, B)

@@ -19,7 +19,6 @@
 #include "philox_random.hip"
 #include "gemm.hip"
 #include "gemm8.hip"
-#include "attention_bwd.hip"
 #include "attention_fwd.hip"
 #include "attention_bwd2.hip"
 #include "attention_gen.hip"
@@ -548,7 +547,7 @@ FaShape fa_check(const Binding& b, int tile, const at::Tensor& q, const at::Tens
   b.arg("lse", lse, F32, {B, Hq, S});
   return {(int)B, (int)Hq, (int)Hkv, (int)S};
 }
-static_assert(FA_D == FF_D && FB_D == FF_D, "tuned attention kernels share D");
+static_assert(FB_D == FF_D, "tuned attention kernels share D");
 
 // out_bshd: o is allocated and written as [B,S,Hq,D]; lse stays [B,Hq,S]
 std::vector<at::Tensor> fa_fwd_impl(const Binding& b, int64_t mode, at::Tensor q,
@@ -581,8 +580,7 @@ std::vector<at::Tensor> fa_fwd_ablate(at::Tensor q, at::Tensor k, at::Tensor v,
   return fa_fwd_impl(Binding("fa_fwd_ablate", "q", q), mode, q, k, v, scale, false);
 }
 
-// delta[b,h,s] = sum_d dout * o, shared by both tuned backwards; bshd: dout
-// and o are [B,S,Hq,D]
+// delta[b,h,s] = sum_d dout * o for fa_bwd2; bshd: dout and o are [B,S,Hq,D]
 at::Tensor fa_bwd_delta(const Binding& b, const FaShape& s, const at::Tensor& dout,
                         const at::Tensor& o, bool bshd = false) {
   auto delta = at::empty({s.B, s.Hq, s.S}, o.options().dtype(F32));
@@ -600,25 +598,6 @@ at::Tensor fa_bwd_reduce(const Binding& b, const FaShape& s, const at::Tensor& p
   b.launch(fa_bwd_reduce_gqa, grid_for((int64_t)s.B * s.Hkv * SD / 8, 256), 256,
            bf16(part), bf16_mut(out), s.B, s.Hq, s.Hkv, SD);
   return out;
-}
-
-// ------------------------------ flash-attention backward -------------------
-std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
-                               at::Tensor dout, at::Tensor lse, double scale) {
-  Binding b("fa_bwd", "q", q);
-  FaShape s = fa_check(b, FA_BLK, q, k, v, o, dout, lse);
-  auto delta = fa_bwd_delta(b, s, dout, o);
-  auto dq = at::empty_like(q);
-  auto dk_part = at::empty_like(q);
-  auto dv_part = at::empty_like(q);
-  dim3 gridkv(s.S / FA_BLK, s.Hq, s.B);
-  b.launch(fa_bwd_dkdv, gridkv, FA_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
-           lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dk_part),
-           bf16_mut(dv_part), s.B, s.Hq, s.Hkv, s.S, (float)scale);
-  b.launch(fa_bwd_dq, gridkv, FA_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
-           lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), s.B, s.Hq,
-           s.Hkv, s.S, (float)scale);
-  return {dq, fa_bwd_reduce(b, s, dk_part), fa_bwd_reduce(b, s, dv_part)};
 }
 
 // ------------------------------ flash-attention backward v2 ---------------
@@ -729,6 +708,15 @@ std::vector<at::Tensor> fa_gen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
            bf16_mut(dq), s.Hq, s.Hkv, s.Sq, s.Sk, (float)scale, causal ? 1 : 0,
            s.shift);
   return {dq, dk, dv};
+}
+
+// fa_gen_bwd behind the tuned kernels' argument checks (causal, D = 128,
+// S % 64 == 0, no dlse)
+std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                               at::Tensor dout, at::Tensor lse, double scale) {
+  fa_check(Binding("fa_bwd", "q", q), FG_BLK, q, k, v, o, dout, lse);
+  TORCH_CHECK(q.is_cuda(), "fa_bwd: argument 'q' expected device=a GPU; got device=", q.device());
+  return fa_gen_bwd(q, k, v, o, dout, lse, {}, scale, true, 0);
 }
 
 // ------------------------------ philox random ------------------------------
