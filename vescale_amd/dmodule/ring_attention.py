@@ -84,30 +84,41 @@ def _merge(acc, lse, block_out, block_lse):
     return acc, new_lse
 
 
-def _ring_flash(ql, kl, vl, group, p, my, is_causal, scale):
+def _ring_flash(ql, kl, vl, group, p, my, is_causal, scale, seg=None):
     """Ring loop over ops.flash_attention blocks.  k/v circulate with their
     own Hkv heads.  Every rank runs every block (so the shift nodes'
     backward pairs up); a future block (j > my) is passed with a shift that
     masks it wholly, and flash_attention's dead-row semantics (out = 0,
     lse = -inf, zero grads) make it a no-op in the merge.  The running
     (acc, lse) pair is fp32 and seeded from step 0 — the diagonal block,
-    whose rows are all live — so the merge never sees -inf on both sides."""
+    whose rows are all live — so the merge never sees -inf on both sides.
+
+    seg: this rank's [B, S_local] segment ids.  The q ids stay put; the kv
+    ids travel the ring next to k/v as a plain tensor (no autograd node:
+    ids have no gradient) and go into every block call.  A query's own key
+    carries its id, so the diagonal block's rows stay live; in a past block
+    that holds nothing of a query's document the row is dead and the merge
+    ignores it."""
     from ..ops import flash_attention
 
     s_local = ql.shape[2]
     k_cur, v_cur = kl, vl
+    seg_cur = seg
     acc = lse = None
     for step in range(p):
         j = (my - step) % p  # global kv-block index currently held
         if step != p - 1:
             k_nxt = _RingShift.apply(k_cur, group)
             v_nxt = _RingShift.apply(v_cur, group)
+            if seg is not None:
+                seg_nxt = _shift(seg_cur, group, forward=True)
         masked = is_causal and j >= my  # past blocks (j < my) are fully visible
         block_out, block_lse = flash_attention(
             ql, k_cur, v_cur,
             is_causal=masked,
             causal_shift=(my - j) * s_local if masked else 0,
             scale=scale, return_lse=True,
+            q_segment_ids=seg, kv_segment_ids=seg_cur,
         )
         block_out = block_out.float()
         block_lse = block_lse.float().unsqueeze(-1)
@@ -117,6 +128,8 @@ def _ring_flash(ql, kl, vl, group, p, my, is_causal, scale):
             acc, lse = _merge(acc, lse, block_out, block_lse)
         if step != p - 1:
             k_cur, v_cur = k_nxt, v_nxt
+            if seg is not None:
+                seg_cur = seg_nxt
     return acc.to(ql.dtype)
 
 
@@ -129,6 +142,7 @@ def ring_sdpa(
     scale: Optional[float] = None,
     seq_dim: int = 2,
     impl: str = "eager",
+    segment_ids: Optional[torch.Tensor] = None,
 ) -> DTensor:
     """Exact sequence-parallel attention with ring-circulated KV.
 
@@ -138,8 +152,14 @@ def ring_sdpa(
     enable_gqa.  impl="flash" computes each block with ops.flash_attention
     (see the module docstring's memory note); it needs the default
     [B, H, S, D] layout (seq_dim == 2).
+
+    segment_ids: this rank's local [B, S_local] slice (a plain integer
+    tensor) of the packed rows' [B, S] segment ids; a token attends only to
+    tokens with its own id, across ranks too.  impl="flash" only.
     """
     assert impl in ("eager", "flash"), f"unknown impl {impl!r}"
+    if segment_ids is not None and impl != "flash":
+        raise ValueError("ring_sdpa: segment_ids needs impl='flash'")
     mesh = q.device_mesh
     assert mesh.ndim == 1, "ring_sdpa runs over a 1-D (SP) mesh"
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -156,7 +176,14 @@ def ring_sdpa(
     assert Hq % Hk == 0, "query heads must be a multiple of kv heads (GQA)"
     if impl == "flash":
         assert seq_dim == 2, "impl='flash' needs the [B, H, S, D] layout"
-        out = _ring_flash(ql, kl, vl, group, p, my, is_causal, scale)
+        seg = None
+        if segment_ids is not None:
+            if tuple(segment_ids.shape) != (B, Sq):
+                raise ValueError(
+                    f"ring_sdpa: segment_ids must be the local [B, S_local] = "
+                    f"[{B}, {Sq}] slice, got {list(segment_ids.shape)}")
+            seg = segment_ids.to(torch.int32).contiguous()
+        out = _ring_flash(ql, kl, vl, group, p, my, is_causal, scale, seg)
         return DTensor.from_local(out, mesh, [Shard(seq_dim)])
     if Hk != Hq:
         rep = Hq // Hk
@@ -213,6 +240,7 @@ class RingAttention(torch.nn.Module):
         self.scale = scale
         self.impl = impl
 
-    def forward(self, q: DTensor, k: DTensor, v: DTensor) -> DTensor:
+    def forward(self, q: DTensor, k: DTensor, v: DTensor,
+                segment_ids: Optional[torch.Tensor] = None) -> DTensor:
         return ring_sdpa(q, k, v, is_causal=self.is_causal, scale=self.scale,
-                         impl=self.impl)
+                         impl=self.impl, segment_ids=segment_ids)

@@ -52,6 +52,10 @@ def ulysses_sdpa(
     divide the mesh size.  impl="flash" runs the local attention through
     ops.flash_attention instead of F.scaled_dot_product_attention (needs
     the default [B, H, S, D] dims).
+
+    Packed sequences (segment ids) are out of scope here: there is no
+    segment_ids argument, and ring_sdpa(impl="flash", segment_ids=...) is
+    the sequence-parallel path that masks across documents.
     """
     assert impl in ("sdpa", "flash"), f"unknown impl {impl!r}"
     mesh = q.device_mesh

@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from ..ops import (
     build_rope_table,
     linear as vlinear,
+    flash_attention,
     flash_attention_causal,
     fused_add_rmsnorm,
     fused_cross_entropy,
@@ -124,16 +125,25 @@ class Attention(nn.Module):
             )
             self.wo.weight._tp_shard = (1, cfg.n_heads * hd, [(0, q, r * q)])
 
-    def forward(self, x: torch.Tensor, rope_table: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, rope_table: torch.Tensor,
+                segment_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """segment_ids [B, S] (integers): packed documents; a token attends
+        only to earlier tokens that carry its own id.  RoPE positions stay
+        global: scores depend on relative offsets only, so a packed document
+        computes what it would alone."""
         B, S, _ = x.shape
         cfg = self.cfg
         x = copy_to_tp(x, self.tp)
         qkv = self.wqkv(x)
         # rope_qkv emits [B, H, S, D] directly (attention's native layout)
         q, k, v = rope_qkv(qkv, rope_table, self.hq, self.hkv, cfg.head_dim)
-        # our MFMA flash forward + library backward (ops/functional.py);
-        # falls back to SDPA off-GPU or for unsupported shapes
-        o = flash_attention_causal(q, k, v)
+        if segment_ids is None:
+            # our MFMA flash forward + library backward (ops/functional.py);
+            # falls back to SDPA off-GPU or for unsupported shapes
+            o = flash_attention_causal(q, k, v)
+        else:
+            # document mask: the general HIP kernel (its torch reference off-GPU)
+            o = flash_attention(q, k, v, is_causal=True, q_segment_ids=segment_ids)
         o = o.transpose(1, 2).reshape(B, S, self.hq * cfg.head_dim)
         return reduce_from_tp(self.wo(o), self.tp)
 
@@ -168,7 +178,7 @@ class TransformerBlock(nn.Module):
         self.ffn_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.ffn = FeedForward(cfg, tp)
 
-    def forward(self, h, delta, rope_table):
+    def forward(self, h, delta, rope_table, segment_ids=None):
         # residual stream (h) with a PENDING delta: the add is fused into
         # the next norm's read pass (ops.fused_add_rmsnorm) — saves a full
         # read+write of the hidden state per residual add
@@ -177,7 +187,7 @@ class TransformerBlock(nn.Module):
             None if delta is None else h,
             self.attn_norm.weight, self.attn_norm.eps,
         )
-        a = self.attn(y, rope_table)
+        a = self.attn(y, rope_table, segment_ids)
         y2, h = fused_add_rmsnorm(a, h, self.ffn_norm.weight, self.ffn_norm.eps)
         return h, self.ffn(y2)
 
@@ -230,17 +240,25 @@ class LlamaModel(nn.Module):
         tokens: torch.Tensor,
         targets: Optional[torch.Tensor] = None,
         ignore_index: int = -100,
+        segment_ids: Optional[torch.Tensor] = None,
     ):
+        """segment_ids [B, S] (integers, e.g. from
+        ops.segment_ids_from_cu_seqlens): several documents packed into one
+        row; every attention layer masks across documents, so each document
+        computes what it would alone.  None leaves the unpacked path as it
+        is.  The loss is not told about documents: the caller sets
+        `ignore_index` on the last target of each document (its next token
+        belongs to another document) and on padding."""
         h = self.tok_embeddings(tokens)
         tab = self.rope_table
         delta = None
         for layer in self.layers:
             if self.activation_checkpointing and self.training:
                 h, delta = torch.utils.checkpoint.checkpoint(
-                    layer, h, delta, tab, use_reentrant=False
+                    layer, h, delta, tab, segment_ids, use_reentrant=False
                 )
             else:
-                h, delta = layer(h, delta, tab)
+                h, delta = layer(h, delta, tab, segment_ids)
         h, _ = fused_add_rmsnorm(
             h if delta is None else delta,
             None if delta is None else h,

@@ -184,8 +184,9 @@ class MixtralBlock(nn.Module):
         self.ffn_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.moe = MoELayer(cfg)
 
-    def forward(self, x, rope_table):
-        x = x + self.attn(self.attn_norm(x), rope_table)
+    def forward(self, x, rope_table, segment_ids=None):
+        # segment_ids [B, S]: the document mask of llama.Attention
+        x = x + self.attn(self.attn_norm(x), rope_table, segment_ids)
         x = x + self.moe(self.ffn_norm(x))
         return x
 
@@ -213,10 +214,14 @@ class MixtralModel(nn.Module):
             else:
                 nn.init.zeros_(p)
 
-    def forward(self, tokens, targets=None, ignore_index: int = -100):
+    def forward(self, tokens, targets=None, ignore_index: int = -100, segment_ids=None):
+        """segment_ids [B, S]: packed documents, masked across documents in
+        every attention layer as in LlamaModel.forward (the caller sets
+        `ignore_index` on the last target of each document).  The router
+        sees every token as before."""
         h = self.tok_embeddings(tokens)
         for layer in self.layers:
-            h = layer(h, self.rope_table)
+            h = layer(h, self.rope_table, segment_ids)
         h = self.norm(h)
         logits = self.output(h)
         if targets is None:

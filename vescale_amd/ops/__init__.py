@@ -39,6 +39,7 @@ def require_ext():
 from .functional import (  # noqa: E402,F401
     flash_attention,
     flash_attention_causal,
+    segment_ids_from_cu_seqlens,
     fused_cross_entropy,
     vocab_parallel_cross_entropy,
     vp_ce_partials,

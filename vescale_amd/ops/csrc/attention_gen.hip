@@ -20,31 +20,61 @@
 // index arithmetic inside int.  KV (resp. Q) tiles wholly outside the
 // visible range are skipped.
 //
-// Tails: rows >= Sq / >= Sk are never loaded (every global load is
-// predicated on its row) and never stored; staging zero-fills them, and the
-// mask gives their scores no weight.
+// Segment mask (packed documents), the compile-time variant SEG of fwd, dkdv
+// and dq (template <int D, bool SEG>; preprocess needs nothing): with
+// q_seg [B,Sq] and kv_seg [B,Sk] (int32), key j is visible to query i iff
+// kv_seg[b,j] == q_seg[b,i] AND the rule above holds.  Ids are compared for
+// equality only: no value is special and they need not be sorted.  The test
+// is written once, in fg_vis<SEG>.  fa_gen_seg_bounds_kernel writes the
+// (min, max) id of every 64-row q and kv tile first; a (q tile, kv tile) pair
+// whose ranges do not overlap holds no equal pair and its whole loop
+// iteration is skipped — staging and barriers included, on block-uniform
+// scalar facts, for all waves at once.  Conservative for unsorted ids (a
+// pair that is not skipped is masked element by element as ever).  The
+// SEG = false instantiations are the kernels without any of this: the ids
+// and bounds are dead arguments (null), registers and results unchanged.
 //
-// Dead rows (no visible key): o = 0 and lse = -inf exactly; in backward they
-// contribute exactly zero (their P and dS are selected to 0, never computed
-// as exp(-inf - -inf) or 0/0), and dlse is taken as 0 on them.
+// Tails: rows >= Sq / >= Sk are never loaded (every global load is
+// predicated on its row, segment ids included) and never stored; staging
+// zero-fills them, and the mask gives their scores no weight.  A tile's
+// (min, max) leaves its tail rows out.
+//
+// Dead rows (no visible key; with SEG also a query whose id no visible key
+// carries): o = 0 and lse = -inf exactly; in backward they contribute
+// exactly zero (their P and dS are selected to 0, never computed as
+// exp(-inf - -inf) or 0/0), and dlse is taken as 0 on them.  With SEG as
+// without, P and dS of a masked entry are selected to exact 0, so a key that
+// no query sees gets dk = dv = 0 exactly.
 //
 // Backward is the standard split plus the LSE gradient:
 //   fa_gen_preprocess: delta[row] = rowsum(dO*O) - dlse[row] (0 on dead rows)
 //   fa_gen_dkdv:       per KV tile, loops the GQA group in-kernel (fp32
 //                      accumulation across the group, no partial buffers)
 //   fa_gen_dq:         per Q tile
-// No atomics anywhere: repeated calls are bitwise equal.
+// No atomics anywhere, the segment pre-pass included (one wave per tile, a
+// shuffle reduction, one plain store): repeated calls are bitwise equal,
+// with and without segment ids.
 //
 // Build report (hipcc -O3 --offload-arch=gfx950,
 // -Rpass-analysis=kernel-resource-usage): no scratch (0 B/lane) and no
 // SGPR/VGPR spills in any instantiation.
-//   kernel       D    VGPRs  AGPRs  LDS B/block  waves/SIMD (compiler)
-//   fa_gen_fwd   64   98     16     27648        4
-//   fa_gen_fwd   128  154    32     45056        2
-//   fa_gen_dq    64   112    32     27648        3
-//   fa_gen_dq    128  144    56     45056        2
-//   fa_gen_dkdv  64   146    52     37376        2
-//   fa_gen_dkdv  128  201    80     55808        1
+//   kernel       D    SEG  VGPRs  AGPRs  LDS B/block  waves/SIMD (compiler)
+//   fa_gen_fwd   64   -    98     16     27648        4
+//   fa_gen_fwd   128  -    154    32     45056        2
+//   fa_gen_dq    64   -    112    32     27648        3
+//   fa_gen_dq    128  -    144    56     45056        2
+//   fa_gen_dkdv  64   -    146    52     37376        2
+//   fa_gen_dkdv  128  -    201    80     55808        1
+//   fa_gen_fwd   64   yes  118    20     27648        3
+//   fa_gen_fwd   128  yes  159    48     45056        2
+//   fa_gen_dq    64   yes  106    52     27648        3
+//   fa_gen_dq    128  yes  174    36     45056        2
+//   fa_gen_dkdv  64   yes  176    30     37376        2
+//   fa_gen_dkdv  128  yes  248    40     55808        1
+//   fa_gen_seg_bounds      8      0      0            8
+// The segment variants hold 8 ids per lane (4 rows, 4 columns) and the tile
+// ranges; only the forward at D=64 loses a wave per SIMD (4 -> 3) to them.
+// The rows without SEG are those of the build before the segment mask.
 // Occupancy is register-bound, not LDS-bound: at the stated waves/SIMD a CU
 // holds 4 / 2 / 3 / 2 / 2 / 1 four-wave blocks, i.e. at most 110.6 KB
 // (fwd D=64: 4 x 27648) of the 160 KB LDS.  dkdv at D=128 carries two
@@ -61,12 +91,55 @@
 //   B4 H12 S1000 D64 non-causal:     fa_gen 0.300 ms, SDPA 0.228 ms (1.32x slower)
 // The general kernel loses at both: it buys shape coverage, the LSE output
 // and O(S*D) saved state, not speed.
+//
+// Measured with segment ids (profiles/fa_gen_segments.txt; fa_gen_fwd +
+// fa_gen_bwd, B4 Hq32 Hkv8 S8192 D128 causal, median of 12, three runs
+// within 0.2%):
+//   no ids 72.1 ms | ids that mask nothing 75.5 ms (+4.7%: the mask itself)
+//   8 documents of 1024: 15.7 ms (0.218x; 0.132 of the tile pairs visible)
+//   64 documents of 128: 3.08 ms (0.043x; 0.023 of the tile pairs visible)
+// The time falls with the visible share, less than in proportion.  The
+// cause was not isolated by measurement; the likely one is that a block
+// with few tiles to visit no longer amortises its prologue and epilogue.
 #include "fa16_common.h"
+
+#include <climits>
+
+// ---------------------------------------------------------------------------
+// segment pre-pass   grid: (ceil(Sq/64) + ceil(Sk/64), B), one wave per tile
+// bounds[b][tile] = (min, max) of the tile's segment ids, q tiles first
+// (the layout fg_seg_bounds reads).  Tail rows are left out and never read;
+// every tile has at least one row.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(FG_BLK)
+fa_gen_seg_bounds_kernel(const int* __restrict__ q_seg,
+                         const int* __restrict__ kv_seg,
+                         int* __restrict__ bounds, int Sq, int Sk) {
+  const int nqt = fg_tiles(Sq);
+  const int b = blockIdx.y;
+  const bool is_q = (int)blockIdx.x < nqt;
+  const int tile = is_q ? blockIdx.x : blockIdx.x - nqt;
+  const int n = is_q ? Sq : Sk;
+  const int* seg = is_q ? q_seg + (int64_t)b * Sq : kv_seg + (int64_t)b * Sk;
+  const int row = tile * FG_BLK + threadIdx.x;
+  int lo = INT_MAX, hi = INT_MIN;
+  if (row < n) lo = hi = seg[row];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    lo = min(lo, __shfl_xor(lo, off, 64));
+    hi = max(hi, __shfl_xor(hi, off, 64));
+  }
+  if (threadIdx.x == 0) {
+    int* out = bounds + ((int64_t)b * gridDim.x + blockIdx.x) * 2;
+    out[0] = lo;
+    out[1] = hi;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // forward   grid: (ceil(Sq/64), Hq, B)
 // ---------------------------------------------------------------------------
-template <int D>
+template <int D, bool SEG>
 __global__ void __launch_bounds__(FG_THREADS)
 fa_gen_fwd_kernel(const unsigned short* __restrict__ q,
                   const unsigned short* __restrict__ k,
@@ -74,7 +147,10 @@ fa_gen_fwd_kernel(const unsigned short* __restrict__ q,
                   unsigned short* __restrict__ o,
                   float* __restrict__ lse,
                   int Hq, int Hkv, int Sq, int Sk, float scale_log2,
-                  int causal, int shift) {
+                  int causal, int shift,
+                  const int* __restrict__ q_seg,
+                  const int* __restrict__ kv_seg,
+                  const int* __restrict__ seg_bounds) {
   constexpr int FG_LDD = D + FG_PAD;
   constexpr int KC = D / 32;    // contraction chunks over D
   constexpr int NF = D / 16;    // 16-col output blocks over D
@@ -104,9 +180,31 @@ fa_gen_fwd_kernel(const unsigned short* __restrict__ q,
   for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; l[r] = 0.f; }
 
   const int trow = wave * 16 + 4 * (lane >> 4);   // tile row of acc[.][0]
+  // SEG: ids of this lane's 4 query rows / 4 key columns, the q tile's id
+  // range and this batch row's kv ids and kv tile ranges
+  int qs[4] = {0, 0, 0, 0}, ks[4] = {0, 0, 0, 0};
+  int qlo = 0, qhi = 0;
+  const int* ksb = nullptr;
+  const int* kb = nullptr;
+  if constexpr (SEG) {
+    const int* qb;
+    fg_seg_bounds(seg_bounds, b, Sq, Sk, qb, kb);
+    fg_seg_range(qb, blockIdx.x, qlo, qhi);
+    ksb = kv_seg + (int64_t)b * Sk;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) qs[r] = fg_seg(q_seg + (int64_t)b * Sq, q0 + trow + r, Sq);
+  }
   const int n_tiles = fg_kv_tiles(q0, Sq, Sk, causal, shift);
   for (int jt = 0; jt < n_tiles; ++jt) {
     const int k0 = jt * FG_BLK;
+    if constexpr (SEG) {
+      // block-uniform: every wave skips the whole iteration, barriers included
+      int klo, khi;
+      fg_seg_range(kb, jt, klo, khi);
+      if (!fg_seg_overlap(qlo, qhi, klo, khi)) continue;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) ks[f] = fg_seg(ksb, k0 + f * 16 + (lane & 15), Sk);
+    }
     fg_shortx8 regv[NLD];
     fg_stage<D>(kh, k0, Sk, lk, tid);
     fg_tile_load<D>(regv, vh, k0, Sk, tid);
@@ -125,7 +223,8 @@ fa_gen_fwd_kernel(const unsigned short* __restrict__ q,
       int col = k0 + f * 16 + (lane & 15);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float x = fg_vis(q0 + trow + r, col, Sk, causal, shift) ? s[f][r] * scale_log2 : -INFINITY;
+        float x = fg_vis<SEG>(q0 + trow + r, col, Sk, causal, shift, qs[r], ks[f])
+                      ? s[f][r] * scale_log2 : -INFINITY;
         s[f][r] = x;
         mx[r] = fmaxf(mx[r], x);
       }
@@ -213,7 +312,7 @@ fa_gen_preprocess_kernel(const unsigned short* __restrict__ dout,
 // ---------------------------------------------------------------------------
 // backward 2) dK/dV   grid: (ceil(Sk/64), Hkv, B); loops the GQA group
 // ---------------------------------------------------------------------------
-template <int D>
+template <int D, bool SEG>
 __global__ void __launch_bounds__(FG_THREADS)
 fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
                    const unsigned short* __restrict__ k,
@@ -224,7 +323,10 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
                    unsigned short* __restrict__ dk,
                    unsigned short* __restrict__ dv,
                    int Hq, int Hkv, int Sq, int Sk, float scale,
-                   int causal, int shift) {
+                   int causal, int shift,
+                   const int* __restrict__ q_seg,
+                   const int* __restrict__ kv_seg,
+                   const int* __restrict__ seg_bounds) {
   constexpr int FG_LDD = D + FG_PAD;
   constexpr int KC = D / 32;
   constexpr int NF = D / 16;
@@ -263,6 +365,21 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
   // first q row that sees key k0: i >= k0 - shift
   const int iq_start = (causal && k0 - shift > 0) ? (k0 - shift) / FG_BLK : 0;
 
+  // SEG: ids of this lane's 4 key rows / 4 query columns, the kv tile's id
+  // range and this batch row's q ids and q tile ranges
+  int ks[4] = {0, 0, 0, 0}, qs[4] = {0, 0, 0, 0};
+  int klo = 0, khi = 0;
+  const int* qsb = nullptr;
+  const int* qb = nullptr;
+  if constexpr (SEG) {
+    const int* kb;
+    fg_seg_bounds(seg_bounds, b, Sq, Sk, qb, kb);
+    fg_seg_range(kb, blockIdx.x, klo, khi);
+    qsb = q_seg + (int64_t)b * Sq;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ks[r] = fg_seg(kv_seg + (int64_t)b * Sk, k0 + trow + r, Sk);
+  }
+
   for (int g = 0; g < group; ++g) {
     const int h = hkv * group + g;
     const unsigned short* qh = q + ((int64_t)b * Hq + h) * Sq * D;
@@ -272,6 +389,14 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
 
     for (int iq = iq_start; iq < n_qtiles; ++iq) {
       const int q0 = iq * FG_BLK;
+      if constexpr (SEG) {
+        // block-uniform: every wave skips the whole iteration, barriers included
+        int qlo, qhi;
+        fg_seg_range(qb, iq, qlo, qhi);
+        if (!fg_seg_overlap(qlo, qhi, klo, khi)) continue;
+#pragma unroll
+        for (int f = 0; f < 4; ++f) qs[f] = fg_seg(qsb, q0 + f * 16 + (lane & 15), Sq);
+      }
       fg_shortx8 regq[NLD], regdo[NLD];
       fg_stage<D>(regq, qh, q0, Sq, lq, tid);
       fg_stage<D>(regdo, doh, q0, Sq, ldo, tid);
@@ -294,7 +419,7 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
         float dl = dlt_s[qc];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          bool vis = fg_vis(q0 + qc, k0 + trow + r, Sk, causal, shift);
+          bool vis = fg_vis<SEG>(q0 + qc, k0 + trow + r, Sk, causal, shift, qs[f], ks[r]);
           float p = fg_p(vis, st[f][r], scale_log2, l2);
           lpt[(trow + r) * FG_ROWS_N + qc] = f32_to_bf16(p);
           ldst[(trow + r) * FG_ROWS_N + qc] = f32_to_bf16(fg_ds(p, dpt[f][r], dl, scale));
@@ -317,7 +442,7 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
 // ---------------------------------------------------------------------------
 // backward 3) dQ   grid: (ceil(Sq/64), Hq, B)
 // ---------------------------------------------------------------------------
-template <int D>
+template <int D, bool SEG>
 __global__ void __launch_bounds__(FG_THREADS)
 fa_gen_dq_kernel(const unsigned short* __restrict__ q,
                  const unsigned short* __restrict__ k,
@@ -327,7 +452,10 @@ fa_gen_dq_kernel(const unsigned short* __restrict__ q,
                  const float* __restrict__ delta,
                  unsigned short* __restrict__ dq,
                  int Hq, int Hkv, int Sq, int Sk, float scale,
-                 int causal, int shift) {
+                 int causal, int shift,
+                 const int* __restrict__ q_seg,
+                 const int* __restrict__ kv_seg,
+                 const int* __restrict__ seg_bounds) {
   constexpr int FG_LDD = D + FG_PAD;
   constexpr int KC = D / 32;
   constexpr int NF = D / 16;
@@ -363,9 +491,30 @@ fa_gen_dq_kernel(const unsigned short* __restrict__ q,
   fg_floatx4 accQ[NF];
   fg_zero(accQ);
 
+  // SEG: as in the forward
+  int qs[4] = {0, 0, 0, 0}, ks[4] = {0, 0, 0, 0};
+  int qlo = 0, qhi = 0;
+  const int* ksb = nullptr;
+  const int* kb = nullptr;
+  if constexpr (SEG) {
+    const int* qb;
+    fg_seg_bounds(seg_bounds, b, Sq, Sk, qb, kb);
+    fg_seg_range(qb, blockIdx.x, qlo, qhi);
+    ksb = kv_seg + (int64_t)b * Sk;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) qs[r] = fg_seg(q_seg + (int64_t)b * Sq, q0 + trow + r, Sq);
+  }
   const int n_tiles = fg_kv_tiles(q0, Sq, Sk, causal, shift);
   for (int jt = 0; jt < n_tiles; ++jt) {
     const int k0 = jt * FG_BLK;
+    if constexpr (SEG) {
+      // block-uniform: every wave skips the whole iteration, barriers included
+      int klo, khi;
+      fg_seg_range(kb, jt, klo, khi);
+      if (!fg_seg_overlap(qlo, qhi, klo, khi)) continue;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) ks[f] = fg_seg(ksb, k0 + f * 16 + (lane & 15), Sk);
+    }
     fg_shortx8 regk[NLD];
     fg_stage<D>(regk, kh, k0, Sk, lk, tid);
     fg_stage<D>(vh, k0, Sk, lv, tid);
@@ -385,7 +534,7 @@ fa_gen_dq_kernel(const unsigned short* __restrict__ q,
       int col = k0 + f * 16 + (lane & 15);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        bool vis = fg_vis(q0 + trow + r, col, Sk, causal, shift);
+        bool vis = fg_vis<SEG>(q0 + trow + r, col, Sk, causal, shift, qs[r], ks[f]);
         float p = fg_p(vis, s[f][r], scale_log2, l2_r[r]);
         lds_s[(trow + r) * FG_ROWS_N + f * 16 + (lane & 15)] =
             f32_to_bf16(fg_ds(p, dp[f][r], dlt_r[r], scale));

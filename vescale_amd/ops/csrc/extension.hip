@@ -33,6 +33,7 @@ namespace {
 constexpr auto BF16 = at::kBFloat16;
 constexpr auto F32 = at::kFloat;
 constexpr auto I64 = at::kLong;
+constexpr auto I32 = at::kInt;
 using OptTensor = c10::optional<at::Tensor>;
 
 // typed pointers (bf16 travels as unsigned short); an absent optional is null
@@ -638,10 +639,11 @@ std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Te
 }
 
 // ------------------------------ general-shape flash attention --------------
-struct FaGenShape { int B, Hq, Hkv, Sq, Sk, D, shift; };
+struct FaGenShape { int B, Hq, Hkv, Sq, Sk, D, shift; bool seg; };
 
 FaGenShape fa_gen_check(const Binding& b, const at::Tensor& q, const at::Tensor& k,
-                        const at::Tensor& v, bool causal, int64_t shift) {
+                        const at::Tensor& v, bool causal, int64_t shift,
+                        const OptTensor& q_seg, const OptTensor& kv_seg) {
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
               b.fn, ": q, k, v must be [B, H, S, D]");
   int64_t D = q.size(3);
@@ -653,38 +655,75 @@ FaGenShape fa_gen_check(const Binding& b, const at::Tensor& q, const at::Tensor&
               b.fn, ": B and Hq must be in [1, 65535]");
   TORCH_CHECK(q.size(2) + k.size(2) < (int64_t)1 << 30, b.fn, ": sequence too long");
   TORCH_CHECK(causal || shift == 0, b.fn, ": shift needs causal");
+  TORCH_CHECK(q_seg.has_value() == kv_seg.has_value(), b.fn,
+              ": q_seg and kv_seg must be given together");
   b.arg("q", q, BF16);
   b.arg("k", k, BF16, {q.size(0), -1, -1, D});  // [B, Hkv, Sk, D]
   b.arg("v", v, BF16, k.sizes());
+  b.arg("q_seg", q_seg, I32, {q.size(0), q.size(2)});    // [B, Sq]
+  b.arg("kv_seg", kv_seg, I32, {q.size(0), k.size(2)});  // [B, Sk]
   // clamping to [-Sq, Sk] leaves the mask j <= i + shift unchanged
   int64_t sh = std::max<int64_t>(-q.size(2), std::min<int64_t>(k.size(2), shift));
   return {(int)q.size(0), (int)q.size(1), (int)k.size(1), (int)q.size(2),
-          (int)k.size(2), (int)D, (int)sh};
+          (int)k.size(2), (int)D, (int)sh, q_seg.has_value()};
 }
 
-// The one place that picks a general kernel's head-dim instantiation.
+// The one place that picks a general kernel's instantiation: head dim, and
+// the segment-masked variant when the call carries segment ids.
 #define FA_GEN_KERNEL(kernel, D) ((D) == 64 ? kernel<64> : kernel<128>)
+#define FA_GEN_KERNEL_SEG(kernel, s)                                        \
+  ((s).seg ? ((s).D == 64 ? kernel<64, true> : kernel<128, true>)           \
+           : ((s).D == 64 ? kernel<64, false> : kernel<128, false>))
+
+// Segment pre-pass: (min, max) id of every 64-row q and kv tile, the facts
+// the kernels skip tile pairs on.  Launched by both bindings (the backward
+// re-runs it: nothing crosses the autograd node but the ids themselves).
+// Without segment ids there is no launch and the kernels get null pointers.
+struct FaGenSeg {
+  at::Tensor bounds;
+  const int* q = nullptr;
+  const int* kv = nullptr;
+  const int* tiles = nullptr;
+};
+
+FaGenSeg fa_gen_seg(const Binding& b, const FaGenShape& s, const at::Tensor& like,
+                    const OptTensor& q_seg, const OptTensor& kv_seg) {
+  FaGenSeg g;
+  if (!s.seg) return g;
+  int tiles = (s.Sq + FG_BLK - 1) / FG_BLK + (s.Sk + FG_BLK - 1) / FG_BLK;
+  g.bounds = at::empty({s.B, tiles, 2}, like.options().dtype(I32));
+  g.q = q_seg->data_ptr<int>();
+  g.kv = kv_seg->data_ptr<int>();
+  b.launch(fa_gen_seg_bounds_kernel, dim3(tiles, s.B), FG_BLK, g.q, g.kv,
+           g.bounds.data_ptr<int>(), s.Sq, s.Sk);
+  g.tiles = g.bounds.data_ptr<int>();
+  return g;
+}
 
 std::vector<at::Tensor> fa_gen_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                   double scale, bool causal, int64_t shift) {
+                                   double scale, bool causal, int64_t shift,
+                                   OptTensor q_seg, OptTensor kv_seg) {
   // q: [B,Hq,Sq,D]; k,v: [B,Hkv,Sk,D] -> {o [B,Hq,Sq,D], lse [B,Hq,Sq] f32}
+  // q_seg [B,Sq], kv_seg [B,Sk] int32 (both or neither): the segment mask
   Binding b("fa_gen_fwd", "q", q);
-  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift);
+  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift, q_seg, kv_seg);
   auto out = at::empty_like(q);
   auto lse = at::empty({s.B, s.Hq, s.Sq}, q.options().dtype(F32));
-  b.launch(FA_GEN_KERNEL(fa_gen_fwd_kernel, s.D),
+  FaGenSeg g = fa_gen_seg(b, s, q, q_seg, kv_seg);
+  b.launch(FA_GEN_KERNEL_SEG(fa_gen_fwd_kernel, s),
            dim3((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B), FG_THREADS, bf16(q), bf16(k),
            bf16(v), bf16_mut(out), lse.data_ptr<float>(), s.Hq, s.Hkv, s.Sq, s.Sk,
-           (float)(scale * 1.4426950408889634), causal ? 1 : 0, s.shift);
+           (float)(scale * 1.4426950408889634), causal ? 1 : 0, s.shift, g.q, g.kv,
+           g.tiles);
   return {out, lse};
 }
 
 std::vector<at::Tensor> fa_gen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                    at::Tensor o, at::Tensor dout, at::Tensor lse,
                                    OptTensor dlse, double scale, bool causal,
-                                   int64_t shift) {
+                                   int64_t shift, OptTensor q_seg, OptTensor kv_seg) {
   Binding b("fa_gen_bwd", "q", q);
-  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift);
+  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift, q_seg, kv_seg);
   b.arg("o", o, BF16, q.sizes());
   b.arg("dout", dout, BF16, q.sizes());
   b.arg("lse", lse, F32, {s.B, s.Hq, s.Sq});
@@ -694,19 +733,20 @@ std::vector<at::Tensor> fa_gen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
   int64_t rows = (int64_t)s.B * s.Hq * s.Sq;
+  FaGenSeg g = fa_gen_seg(b, s, q, q_seg, kv_seg);
   b.launch(FA_GEN_KERNEL(fa_gen_preprocess_kernel, s.D),
            grid_for(rows, 256 / (s.D / 8), 4096), 256, bf16(dout), bf16(o),
            lse.data_ptr<float>(), f32(dlse), delta.data_ptr<float>(), rows);
-  b.launch(FA_GEN_KERNEL(fa_gen_dkdv_kernel, s.D),
+  b.launch(FA_GEN_KERNEL_SEG(fa_gen_dkdv_kernel, s),
            dim3((s.Sk + FG_BLK - 1) / FG_BLK, s.Hkv, s.B), FG_THREADS, bf16(q), bf16(k),
            bf16(v), bf16(dout), lse.data_ptr<float>(), delta.data_ptr<float>(),
            bf16_mut(dk), bf16_mut(dv), s.Hq, s.Hkv, s.Sq, s.Sk, (float)scale,
-           causal ? 1 : 0, s.shift);
-  b.launch(FA_GEN_KERNEL(fa_gen_dq_kernel, s.D),
+           causal ? 1 : 0, s.shift, g.q, g.kv, g.tiles);
+  b.launch(FA_GEN_KERNEL_SEG(fa_gen_dq_kernel, s),
            dim3((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B), FG_THREADS, bf16(q), bf16(k),
            bf16(v), bf16(dout), lse.data_ptr<float>(), delta.data_ptr<float>(),
            bf16_mut(dq), s.Hq, s.Hkv, s.Sq, s.Sk, (float)scale, causal ? 1 : 0,
-           s.shift);
+           s.shift, g.q, g.kv, g.tiles);
   return {dq, dk, dv};
 }
 
@@ -716,7 +756,7 @@ std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Ten
                                at::Tensor dout, at::Tensor lse, double scale) {
   fa_check(Binding("fa_bwd", "q", q), FG_BLK, q, k, v, o, dout, lse);
   TORCH_CHECK(q.is_cuda(), "fa_bwd: argument 'q' expected device=a GPU; got device=", q.device());
-  return fa_gen_bwd(q, k, v, o, dout, lse, {}, scale, true, 0);
+  return fa_gen_bwd(q, k, v, o, dout, lse, {}, scale, true, 0, {}, {});
 }
 
 // ------------------------------ philox random ------------------------------
@@ -820,11 +860,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_fwd_ablate", &fa_fwd_ablate);
   m.def("fa_gen_fwd", &fa_gen_fwd, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("causal"),
-        pybind11::arg("shift"));
+        pybind11::arg("shift"), pybind11::arg("q_seg") = pybind11::none(),
+        pybind11::arg("kv_seg") = pybind11::none());
   m.def("fa_gen_bwd", &fa_gen_bwd, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("dout"),
         pybind11::arg("lse"), pybind11::arg("dlse"), pybind11::arg("scale"),
-        pybind11::arg("causal"), pybind11::arg("shift"));
+        pybind11::arg("causal"), pybind11::arg("shift"),
+        pybind11::arg("q_seg") = pybind11::none(),
+        pybind11::arg("kv_seg") = pybind11::none());
   m.def("permlane_probe", &permlane_probe);
   m.def("mfma32_probe", &mfma32_probe);
   m.def("tr_probe", &tr_probe);

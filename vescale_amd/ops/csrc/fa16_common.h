@@ -58,6 +58,48 @@ DEV bool fg_vis(int row, int col, int Sk, int causal, int shift) {
   return col < Sk && (!causal || col <= row + shift);
 }
 
+// Segment (document) mask, a compile-time variant of the family: with SEG,
+// key `col` is visible to query `row` iff the rule above holds AND the two
+// rows carry the same segment id.  Ids are compared for equality only; no
+// value is special and they need not be sorted.  Without SEG the ids are
+// dead arguments and the test is the one above.
+template <bool SEG>
+DEV bool fg_vis(int row, int col, int Sk, int causal, int shift, int qs, int ks) {
+  bool vis = fg_vis(row, col, Sk, causal, shift);
+  if constexpr (SEG) vis = vis && qs == ks;
+  return vis;
+}
+
+// segment id of row `row` of one batch row's [n] ids.  Rows past the end are
+// not read; what stands in for them never matters (tail keys fail col < Sk,
+// tail queries are never stored and carry l2 = +inf in backward).
+DEV int fg_seg(const int* seg, int row, int n) { return row < n ? seg[row] : 0; }
+
+// The tile bounds of a call, written by fa_gen_seg_bounds_kernel: per batch
+// row, (min, max) pairs of its ceil(Sq/64) q tiles, then of its ceil(Sk/64)
+// kv tiles.  qb / kb = the pairs of batch row b's q / kv tiles.
+DEV int fg_tiles(int n) { return (n + FG_BLK - 1) / FG_BLK; }
+DEV void fg_seg_bounds(const int* bounds, int b, int Sq, int Sk, const int*& qb,
+                       const int*& kb) {
+  qb = bounds + (int64_t)b * (fg_tiles(Sq) + fg_tiles(Sk)) * 2;
+  kb = qb + 2 * fg_tiles(Sq);
+}
+
+// [min, max] of the segment ids of 64-row tile `tile`.  The index is
+// block-uniform wherever this is called, so these are scalar loads.
+DEV void fg_seg_range(const int* bounds, int tile, int& lo, int& hi) {
+  lo = bounds[2 * tile];
+  hi = bounds[2 * tile + 1];
+}
+
+// A (q tile, kv tile) pair can hold an equal pair of ids only if the two id
+// ranges overlap: conservative for unsorted ids, exact for sorted ones.  A
+// block-uniform fact: the caller skips the whole loop iteration on it,
+// staging and barriers included, for all waves at once (rule 3).
+DEV bool fg_seg_overlap(int qlo, int qhi, int klo, int khi) {
+  return qlo <= khi && klo <= qhi;
+}
+
 template <int N>
 DEV void fg_zero(fg_floatx4 (&acc)[N]) {
 #pragma unroll

@@ -597,12 +597,14 @@ def flash_attention_causal(q, k, v):
 # (ops/csrc/attention_gen.hip): any Sq/Sk, D in {64,128}, MHA/GQA/MQA,
 # optional causal mask  j <= i + causal_shift.
 # ---------------------------------------------------------------------------
-def _attention_ref(q, k, v, is_causal, shift, scale, dtype=None):
+def _attention_ref(q, k, v, is_causal, shift, scale, dtype=None, *, q_seg=None,
+                   kv_seg=None):
     """Differentiable torch attention returning (out, lse): the CPU path and
     the oracle of the general kernel.  Matmuls and softmax run in `dtype`
     (default: fp32, or q's dtype if wider); GQA by head grouping; key j is
-    visible to query i iff j <= i + shift; a row with no visible key gives
-    out = 0, lse = -inf and zero gradients."""
+    visible to query i iff j <= i + shift and, with q_seg [B,Sq] / kv_seg
+    [B,Sk] given, kv_seg[b, j] == q_seg[b, i]; a row with no visible key
+    gives out = 0, lse = -inf and zero gradients."""
     if dtype is None:
         dtype = torch.promote_types(q.dtype, torch.float32)
     B, Hq, Sq, D = q.shape
@@ -613,6 +615,9 @@ def _attention_ref(q, k, v, is_causal, shift, scale, dtype=None):
         i = torch.arange(Sq, device=q.device).unsqueeze(1)
         j = torch.arange(Sk, device=q.device).unsqueeze(0)
         s = s.masked_fill(j > i + shift, float("-inf"))
+    if q_seg is not None:
+        other = q_seg.unsqueeze(2) != kv_seg.unsqueeze(1)       # [B, Sq, Sk]
+        s = s.masked_fill(other[:, None, None], float("-inf"))
     m = s.detach().amax(-1, keepdim=True)
     m = torch.where(m == float("-inf"), torch.zeros_like(m), m)
     e = torch.exp(s - m)
@@ -627,13 +632,18 @@ def _attention_ref(q, k, v, is_causal, shift, scale, dtype=None):
 
 
 class _FlashAttentionGen(torch.autograd.Function):
-    """fa_gen_fwd / fa_gen_bwd: one node with two differentiable outputs."""
+    """fa_gen_fwd / fa_gen_bwd: one node with two differentiable outputs.
+    q_seg / kv_seg (contiguous int32 [B,Sq] / [B,Sk], or both None) are
+    non-differentiable inputs; backward hands the ids themselves to
+    fa_gen_bwd, which derives its tile bounds again."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal, shift):
-        out, lse = _ext().fa_gen_fwd(q, k, v, scale, causal, shift)
+    def forward(ctx, q, k, v, scale, causal, shift, q_seg=None, kv_seg=None):
+        out, lse = _ext().fa_gen_fwd(q, k, v, scale, causal, shift,
+                                     q_seg=q_seg, kv_seg=kv_seg)
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.args = (scale, causal, shift)
+        ctx.seg = (q_seg, kv_seg)
         ctx.set_materialize_grads(False)
         return out, lse
 
@@ -641,17 +651,62 @@ class _FlashAttentionGen(torch.autograd.Function):
     def backward(ctx, dout, dlse):
         q, k, v, out, lse = ctx.saved_tensors
         scale, causal, shift = ctx.args
+        q_seg, kv_seg = ctx.seg
         dout = torch.zeros_like(out) if dout is None else dout.contiguous()
         if dlse is not None:
             dlse = dlse.float().contiguous()
         dq, dk, dv = _ext().fa_gen_bwd(
-            q, k, v, out, dout, lse, dlse, scale, causal, shift
+            q, k, v, out, dout, lse, dlse, scale, causal, shift,
+            q_seg=q_seg, kv_seg=kv_seg
         )
-        return dq, dk, dv, None, None, None
+        return dq, dk, dv, None, None, None, None, None
+
+
+def _segment_args(q_segment_ids, kv_segment_ids, B, Sq, Sk):
+    """flash_attention's segment-id rules: (q_seg, kv_seg) as contiguous
+    int32 [B,Sq] / [B,Sk], or (None, None)."""
+    if q_segment_ids is None and kv_segment_ids is None:
+        return None, None
+    if q_segment_ids is None:
+        raise ValueError("kv_segment_ids given without q_segment_ids")
+    if kv_segment_ids is None:
+        if Sq != Sk:
+            raise ValueError(
+                f"kv_segment_ids is required when Sq != Sk ({Sq} != {Sk})")
+        kv_segment_ids = q_segment_ids
+    out = []
+    for name, t, S in (("q_segment_ids", q_segment_ids, Sq),
+                       ("kv_segment_ids", kv_segment_ids, Sk)):
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise ValueError(f"{name} must have an integer dtype, got {t.dtype}")
+        if tuple(t.shape) != (B, S):
+            raise ValueError(f"{name} must be [B, S] = [{B}, {S}], got {list(t.shape)}")
+        out.append(t.to(torch.int32).contiguous())
+    return out[0], out[1]
+
+
+def segment_ids_from_cu_seqlens(cu_seqlens, total: int) -> torch.Tensor:
+    """Segment ids [total] (int32) of a packed row from the varlen
+    convention: cu_seqlens = [0, e_0, e_1, ...] (non-decreasing), document d
+    covering positions [cu_seqlens[d], cu_seqlens[d + 1]).  Positions past
+    cu_seqlens[-1] (padding) get one id of their own, so padding attends
+    only to padding."""
+    cu = torch.as_tensor(cu_seqlens)
+    if cu.dim() != 1 or cu.numel() < 1:
+        raise ValueError("cu_seqlens must be a non-empty 1-D sequence")
+    if cu.dtype.is_floating_point or cu.dtype == torch.bool:
+        raise ValueError(f"cu_seqlens must have an integer dtype, got {cu.dtype}")
+    if int(cu[-1]) > total:
+        raise ValueError(f"cu_seqlens[-1] = {int(cu[-1])} is past total = {total}")
+    pos = torch.arange(total, device=cu.device)
+    # id = number of document ends at or before the position: document d has
+    # d ends before it, the padding tail len(cu) - 1 of them
+    ids = torch.searchsorted(cu[1:].to(torch.int64).contiguous(), pos, right=True)
+    return ids.to(torch.int32)
 
 
 def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
-                    return_lse=False):
+                    return_lse=False, q_segment_ids=None, kv_segment_ids=None):
     """Attention over q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (Hq % Hkv == 0).
 
     With is_causal, key j is visible to query i iff j <= i + causal_shift
@@ -660,16 +715,26 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
     Returns out, or (out, lse) with lse [B,Hq,Sq] fp32 (natural log) when
     return_lse; both outputs are differentiable.
 
-    Dispatch: (1) the tuned D=128 causal kernels when their gate holds and
-    no lse is wanted; (2) the general HIP kernel for bf16 on GPU with D in
-    {64, 128}; (3) the torch reference (CPU, other dtypes / head dims,
-    VESCALE_FA=aten)."""
+    Packed sequences: with q_segment_ids [B,Sq] and kv_segment_ids [B,Sk]
+    (any integer dtype) key j is visible to query i iff, in addition,
+    kv_segment_ids[b, j] == q_segment_ids[b, i].  Ids are compared for
+    equality only: no value is special and they need not be sorted.
+    kv_segment_ids may be left out when Sq == Sk (the same ids for both);
+    otherwise both are required (ValueError).  A query whose id no visible
+    key carries is a dead row as above; a key no query sees gets zero dk/dv.
+    segment_ids_from_cu_seqlens builds ids from document boundaries.
+
+    Dispatch: (1) the tuned D=128 causal kernels when their gate holds, no
+    lse is wanted and there are no segment ids; (2) the general HIP kernel
+    for bf16 on GPU with D in {64, 128}; (3) the torch reference (CPU, other
+    dtypes / head dims, VESCALE_FA=aten)."""
     import math
 
     if causal_shift != 0 and not is_causal:
         raise ValueError("causal_shift != 0 requires is_causal=True")
     B, Hq, Sq, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
+    q_seg, kv_seg = _segment_args(q_segment_ids, kv_segment_ids, B, Sq, Sk)
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     hip = (
@@ -680,7 +745,7 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
         and _use_hip(q, k, v)
     )
     if (hip and not return_lse and is_causal and causal_shift == 0
-            and Sq == Sk and D == 128 and Sq % 256 == 0):
+            and Sq == Sk and D == 128 and Sq % 256 == 0 and q_seg is None):
         return _FlashAttention.apply(
             q.contiguous(), k.contiguous(), v.contiguous(), scale
         )
@@ -688,9 +753,11 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
         out, lse = _FlashAttentionGen.apply(
             q.contiguous(), k.contiguous(), v.contiguous(), float(scale),
             bool(is_causal), int(causal_shift),
+            q_seg, kv_seg,
         )
     else:
-        out, lse = _attention_ref(q, k, v, is_causal, causal_shift, scale)
+        out, lse = _attention_ref(q, k, v, is_causal, causal_shift, scale,
+                                  q_seg=q_seg, kv_seg=kv_seg)
     return (out, lse) if return_lse else out
 
 
