@@ -161,6 +161,7 @@ def test_adamw_clip_fused():
     n = 4096
     p = torch.randn(n, device="cuda").bfloat16()
     master = p.float().clone()
+    master2 = master.clone()
     g = torch.randn(n, device="cuda", dtype=torch.bfloat16)
     m = torch.zeros(n, device="cuda")
     v = torch.zeros(n, device="cuda")
@@ -173,6 +174,13 @@ def test_adamw_clip_fused():
     gf = g.float() * 0.5
     m2.add_(gf, alpha=0.1)
     assert torch.allclose(m, m2, atol=1e-6)
+    # v, master and param as well, at test_adamw_flat's tolerances (defaults:
+    # beta2 0.95, eps 1e-8, no weight decay); param is the rounded master
+    v2.addcmul_(gf, gf, value=0.05)
+    assert torch.allclose(v, v2, atol=1e-7)
+    master2.addcdiv_(m2, (v2 / (1 - 0.95)).sqrt().add_(1e-8), value=-1e-3 / (1 - 0.9))
+    assert torch.allclose(master, master2, atol=1e-5, rtol=1e-4)
+    assert torch.equal(p, master.bfloat16())
 
 
 @requires_gpu
@@ -543,6 +551,15 @@ def test_sharded_dropout_bitwise_tp_parity():
         shard, [64, 128], [32, 128], [16, 0], 0, False, 777, 0, 0.3, True
     )
     assert torch.equal(out, full[16:48])
+
+    # a second op on both sides: the tracker has advanced by the counters the
+    # first op consumed, ceil(global numel / 4), the same on every rank
+    full2 = torch.nn.functional.dropout(d_full, p=0.3, training=True)._local_tensor
+    out2, _ = C.philox_dropout(
+        shard, [64, 128], [32, 128], [16, 0], 0, False, 777, (64 * 128 + 3) // 4, 0.3, True
+    )
+    assert torch.equal(out2, full2[16:48])
+    assert not torch.equal(full2, full)
 
     from vescale_amd.dtensor.dispatch import get_dispatcher
 

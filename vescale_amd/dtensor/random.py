@@ -16,6 +16,7 @@ identical values on all ranks; sharded tensors draw distinct streams.
 from __future__ import annotations
 
 import contextlib
+import math
 from typing import Optional
 
 import torch
@@ -103,7 +104,9 @@ class ThreadBasedRNGTracker(OffsetBasedRNGTracker):
     semantics): random aten ops on GPU DTensors are
     EXECUTED by our sharded-philox HIP kernels with the shard's GLOBAL
     element indexing, so a TP/DP-sharded random fill is bitwise-identical
-    to our own single-GPU fill.  Ops without a philox implementation fall
+    to our own single-GPU fill.  Each op advances the philox offset by the
+    counters it consumes, ceil(global numel / 4), so consecutive ops draw
+    from disjoint counter ranges.  Ops without a philox implementation fall
     back to OffsetBased semantics."""
 
     def current_spec(self) -> Optional[DTensorSpec]:
@@ -163,7 +166,10 @@ class ThreadBasedRNGTracker(OffsetBasedRNGTracker):
         gshape, lshape, offs, foff, flat = d
         seed = self.seed
         philox_off = self._offset
-        self._offset += 4
+        # one unit of offset is one philox counter (four elements): advance by
+        # what this op consumes of the GLOBAL tensor, so that the next op
+        # starts on fresh counters and every rank agrees on where
+        self._offset += (math.prod(spec.shape) + 3) // 4
         pkt = op.overloadpacket
         if pkt == aten.native_dropout:
             p = float(local_args[1])

@@ -34,7 +34,11 @@ DEV unsigned short f32_to_bf16(float f) {
   // round-to-nearest-even
   unsigned int lsb = (v.i >> 16) & 1;
   v.i += 0x7fffu + lsb;
-  return (unsigned short)(v.i >> 16);
+  // a NaN stays a NaN: the increment carries out of a mantissa of all ones
+  // (0x7FFFFFFF -> 0x8000, -0.0; 0xFFFFFFFF -> 0x0000).  Costs a compare and
+  // a select per conversion and 0-2 VGPRs per kernel
+  // (profiles/streaming_edges_gpu.txt).
+  return f != f ? (unsigned short)0x7fc0u : (unsigned short)(v.i >> 16);
 }
 
 // ---------------- wave / block reductions ----------------

@@ -12,6 +12,9 @@
 
 #define BLOCK 256
 
+// a row of all -inf (or an idle thread) must not turn exp(-inf - -inf) into NaN
+DEV float ce_finite_max(float m) { return m == -INFINITY ? 0.f : m; }
+
 // logits: [N, V] bf16; target: [N] int64; loss/lse: [N] f32
 extern "C" __global__ void __launch_bounds__(BLOCK)
 ce_fwd_bf16(const unsigned short* __restrict__ logits,
@@ -35,14 +38,17 @@ ce_fwd_bf16(const unsigned short* __restrict__ logits,
           int col = i + j;
           float f = (col < vocab) ? bf16_to_f32((unsigned short)v[j]) : -INFINITY;
           float m2 = fmaxf(mx, f);
-          sum = sum * __expf(mx - m2) + ((col < vocab) ? __expf(f - m2) : 0.f);
+          // -inf logits (masked classes) while mx is still -inf: shift by 0,
+          // not by -inf (exp(-inf - -inf) is NaN); bitwise the same otherwise
+          float ms = ce_finite_max(m2);
+          sum = sum * __expf(mx - ms) + ((col < vocab) ? __expf(f - ms) : 0.f);
           mx = m2;
         }
       }
     }
     // block combine (max then rescaled sums)
     float gmax = block_reduce_max<BLOCK>(mx, lds);
-    float gsum = block_reduce_sum<BLOCK>(sum * __expf(mx - gmax), lds);
+    float gsum = block_reduce_sum<BLOCK>(sum * __expf(mx - ce_finite_max(gmax)), lds);
     float lse = gmax + __logf(gsum);
     if (threadIdx.x == 0) {
       if (tgt == ignore_index) {
@@ -115,14 +121,11 @@ ce_bwd_bf16(const unsigned short* __restrict__ logits,
 //
 // hipcc -O3 --offload-arch=gfx950 (-Rpass-analysis=kernel-resource-usage):
 //   ce_vp_fwd_bf16: 49 VGPRs, 16 B LDS, no scratch, 8 waves/SIMD
-//   ce_vp_bwd_bf16: 41 VGPRs,  0 B LDS, no scratch, 8 waves/SIMD
-// (dense pair, for comparison: 32 / 29 VGPRs, 8 waves/SIMD)
+//   ce_vp_bwd_bf16: 42 VGPRs,  0 B LDS, no scratch, 8 waves/SIMD
+// (dense pair, for comparison: 31 / 30 VGPRs, 8 waves/SIMD)
 // ---------------------------------------------------------------------------
 #define VP_UNROLL 4
 #define BF16_NEG_INF ((short)0xFF80)
-
-// a row of all -inf (or an idle thread) must not turn exp(-inf - -inf) into NaN
-DEV float vp_finite_max(float m) { return m == -INFINITY ? 0.f : m; }
 
 // logits: [N, n] bf16; target: [N] int64 (global ids); picked/lse_out: [N] f32
 extern "C" __global__ void __launch_bounds__(BLOCK)
@@ -154,7 +157,7 @@ ce_vp_fwd_bf16(const unsigned short* __restrict__ logits,
           vmax = fmaxf(vmax, f[u][j]);
         }
       float m2 = fmaxf(mx, vmax);
-      float ms = vp_finite_max(m2);
+      float ms = ce_finite_max(m2);
       float part = 0.f;
 #pragma unroll
       for (int u = 0; u < VP_UNROLL; ++u)
@@ -164,7 +167,7 @@ ce_vp_fwd_bf16(const unsigned short* __restrict__ logits,
       mx = m2;
     }
     float gmax = block_reduce_max<BLOCK>(mx, lds);
-    float gs = vp_finite_max(gmax);
+    float gs = ce_finite_max(gmax);
     float gsum = block_reduce_sum<BLOCK>(sum * __expf(mx - gs), lds);
     if (threadIdx.x == 0) {
       int64_t tgt = target[row];

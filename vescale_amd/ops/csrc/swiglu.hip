@@ -8,6 +8,15 @@
 
 #define BLOCK 256
 
+// dup = dy * silu(gate), taken as (dy * gate) * sig by all four sites below
+// (so the packed and the separate kernels agree bitwise).  Where dy * gate
+// overflows fp32 while silu(gate) is still small or 0 (gate -3e38, dy 1e18:
+// inf * 0 = NaN) the product is taken as dy * (gate * sig) instead.
+DEV float swiglu_dup(float df, float gf, float sig) {
+  float t = df * gf;
+  return fabsf(t) == INFINITY ? df * (gf * sig) : t * sig;
+}
+
 // PACKED variant: gu = [N, 2F] (gate||up per row, the fused-w13 GEMM
 // output) -> out [N, F]; avoids the split()+contiguous()+cat() round trip
 // torch autograd would otherwise insert (profiled at ~50 ms/step on 8B).
@@ -60,7 +69,7 @@ swiglu_packed_bwd_bf16(const unsigned short* __restrict__ dy,
       float uf = bf16_to_f32((unsigned short)u[j]);
       float sig = 1.0f / (1.0f + __expf(-gf));
       og[j] = (short)f32_to_bf16(df * uf * sig * (1.0f + gf * (1.0f - sig)));
-      ou[j] = (short)f32_to_bf16(df * gf * sig);
+      ou[j] = (short)f32_to_bf16(swiglu_dup(df, gf, sig));
     }
     unsigned short* dbase = dgu + row * 2 * F;
     *reinterpret_cast<short8v*>(dbase + col) = og;
@@ -120,9 +129,8 @@ swiglu_bwd_bf16(const unsigned short* __restrict__ dy,
       float gf = bf16_to_f32((unsigned short)g[j]);
       float uf = bf16_to_f32((unsigned short)u[j]);
       float sig = 1.0f / (1.0f + __expf(-gf));
-      float silu = gf * sig;
       og[j] = (short)f32_to_bf16(df * uf * sig * (1.0f + gf * (1.0f - sig)));
-      ou[j] = (short)f32_to_bf16(df * silu);
+      ou[j] = (short)f32_to_bf16(swiglu_dup(df, gf, sig));
     }
     *reinterpret_cast<short8v*>(dgate + i) = og;
     *reinterpret_cast<short8v*>(dup + i) = ou;
@@ -135,6 +143,6 @@ swiglu_bwd_bf16(const unsigned short* __restrict__ dy,
     float uf = bf16_to_f32(up[t]);
     float sig = 1.0f / (1.0f + __expf(-gf));
     dgate[t] = f32_to_bf16(df * uf * sig * (1.0f + gf * (1.0f - sig)));
-    dup[t] = f32_to_bf16(df * gf * sig);
+    dup[t] = f32_to_bf16(swiglu_dup(df, gf, sig));
   }
 }

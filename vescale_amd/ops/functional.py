@@ -247,6 +247,13 @@ def rope_qkv(qkv: torch.Tensor, table: torch.Tensor, n_heads: int,
 # ---------------------------------------------------------------------------
 # SwiGLU
 # ---------------------------------------------------------------------------
+def _swiglu_dup(d, g, sig):
+    """dy * silu(gate) as the kernels take it (swiglu_dup in swiglu.hip):
+    (dy * gate) * sig, or dy * (gate * sig) where dy * gate overflows."""
+    t = d * g
+    return torch.where(t.isinf(), d * (g * sig), t * sig)
+
+
 class _SwiGLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gate: torch.Tensor, up: torch.Tensor):
@@ -271,7 +278,7 @@ class _SwiGLU(torch.autograd.Function):
         d = dy.float()
         sig = torch.sigmoid(g)
         dgate = (d * u * sig * (1 + g * (1 - sig))).to(gate.dtype)
-        dup = (d * g * sig).to(up.dtype)
+        dup = _swiglu_dup(d, g, sig).to(up.dtype)
         return dgate, dup
 
 
@@ -306,7 +313,7 @@ class _SwiGLUPacked(torch.autograd.Function):
         d = dy.float()
         sig = torch.sigmoid(g)
         dgate = d * u * sig * (1 + g * (1 - sig))
-        dup = d * g * sig
+        dup = _swiglu_dup(d, g, sig)
         return torch.cat([dgate, dup], dim=-1).to(gu.dtype)
 
 
@@ -817,7 +824,8 @@ def scale_flat_(x: torch.Tensor, scale) -> None:
             _ext().scale_(x, None, float(scale))
         return
     if isinstance(scale, torch.Tensor):
-        x.mul_(scale.to(x.dtype))
+        # like the kernel: an fp32 product by the fp32 scale, rounded once
+        x.copy_((x.float() * scale.float()).to(x.dtype))
     else:
         x.mul_(scale)
 
