@@ -20,7 +20,9 @@
 //     the (l&3)-th element of the 64b read issued by lane (l&~3)+j — so
 //     pointing lanes of a group at 4 consecutive kv rows (same d column
 //     group) yields the transposed fragment for free; the row-XOR swizzle
-//     also spreads the 4 rows across banks (2-way worst case)
+//     (fa32_lds_map.h) sends the 4 rows to 4 different 64-byte column
+//     bands, so these reads and the K row-fragment reads are both
+//     bank-conflict-free
 //   - K/V tiles DOUBLE-BUFFERED in LDS: tile j+1's global loads issue
 //     before tile j's compute, stores land in the other buffer, ONE
 //     barrier per tile (guide T3/T4 phase overlap, structured form)

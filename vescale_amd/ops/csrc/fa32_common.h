@@ -1,11 +1,13 @@
 // Shared device helpers of the 32x32x16-MFMA flash-attention family
 // (attention_fwd.hip, attention_bwd2.hip, the tr probe in probes.hip):
-// causal, GQA, D=128, bf16 tiles staged row-major + XOR swizzle in LDS.
+// causal, GQA, D=128, bf16 tiles staged row-major + XOR swizzle in LDS (the
+// map itself, and why it is bank-conflict-free, is fa32_lds_map.h).
 // Every idiom of the family lives HERE, once; the kernels and the probe
 // call it, so the probe exercises the exact code the kernels run
 // (csrc/README.md rule 6).
 #pragma once
 #include "common.h"
+#include "fa32_lds_map.h"
 
 #define FF_D 128
 #define FF_LOG2E 1.44269504088896340736f
@@ -76,11 +78,9 @@ DEV ff_ctx ff_prologue(int Hq, int Hkv, int S) {
 // formula, which the address folding of the row stores depends on.
 #define ff_drow(base, r, half) ((base) + ((r) & 3) + 8 * ((r) >> 2) + 4 * (half))
 
-// Tile LDS swizzle (guide G4): XOR byte-bits 4-6 slot with row bits 0-2
-DEV int ff_kswz(int byte_off) {
-  int row = byte_off >> 8;  // 256B rows ([*][128] bf16)
-  return byte_off ^ ((row & 7) << 4);
-}
+// Tile LDS swizzle (guide G4): XOR the 16-byte slot (byte bits 4-7) with
+// g(row) = ((row & 3) << 2) | ((row >> 2) & 3) — fa32_lds_map.h
+DEV int ff_kswz(int byte_off) { return ff_map_swz(byte_off); }
 
 // Block-cooperative staging of a [ROWS][128] bf16 tile, row-major + ff_kswz,
 // by THREADS threads.  Thread tid moves chunk j = the 8 elements at
@@ -93,12 +93,12 @@ DEV int ff_kswz(int byte_off) {
 // registers in a later pass and the kernel schedules differently.
 #define FF_STAGE_CHUNKS(ROWS, THREADS) ((ROWS) * FF_D / ((THREADS) * 8))
 template <int THREADS>
-DEV int ff_chunk(int j, int tid) { return (tid + j * THREADS) * 8; }
+DEV int ff_chunk(int j, int tid) { return ff_map_chunk(j, tid, THREADS); }
 DEV ff_shortx8 ff_chunk_load(const unsigned short* g, int e) {
   return *reinterpret_cast<const ff_shortx8*>(g + e);
 }
 DEV void ff_chunk_store(ff_shortx8 v, unsigned short* l, int e) {
-  *reinterpret_cast<ff_shortx8*>((char*)l + ff_kswz(e * 2)) = v;
+  *reinterpret_cast<ff_shortx8*>((char*)l + ff_map_chunk_byte(e)) = v;
 }
 template <int ROWS, int THREADS>
 DEV void ff_stage(const unsigned short* __restrict__ g, unsigned short* l, int tid) {
@@ -140,16 +140,15 @@ DEV void ff_stage_rows(const unsigned short* __restrict__ g, int stride, unsigne
 // A-operand fragment: rows s2*32 + l31 of a swizzled [*x128] LDS tile,
 // k = ks*16 + half*8 + e
 DEV ff_shortx8 ff_afrag(const unsigned short* l, int s2, int ks, int l31, int half) {
-  int byte = ((s2 * 32 + l31) * FF_D + ks * 16 + half * 8) * 2;
-  return *reinterpret_cast<const ff_shortx8*>((const char*)l + ff_kswz(byte));
+  return *reinterpret_cast<const ff_shortx8*>((const char*)l +
+                                              ff_map_frag(s2 * 32 + l31, ks, half));
 }
 
 // B-operand fragment of row `row` from a swizzled LDS tile:
 // B[j=row][k = ks*16 + half*8 + e] (row index may exceed 64; swizzle is
-// row-periodic mod 8 so any row count works)
+// row-periodic mod 16 so any multiple of 16 rows works)
 DEV ff_shortx8 ff_bfrag(const unsigned short* l, int row, int ks, int half) {
-  int byte = (row * FF_D + ks * 16 + half * 8) * 2;
-  return *reinterpret_cast<const ff_shortx8*>((const char*)l + ff_kswz(byte));
+  return *reinterpret_cast<const ff_shortx8*>((const char*)l + ff_map_frag(row, ks, half));
 }
 
 // B-operand fragments of one row straight from global memory (the
@@ -211,17 +210,16 @@ DEV void ff_relayout(const ff_floatx16 st[2], ff_shortx8 pb[4], int half) {
 // so lane y reads tile row rbase + ((y&15)>>2) at byte column
 // cbase + (y&3)*4 elems, and the HW hands lane l the column ds*32 + l31 of
 // rows rbase..rbase+3. Two reads (rbase, rbase+4) fill the 8 k elems; ks
-// walks rows in +16 steps = +4096 bytes, which commutes with the bits-4..6
-// row swizzle (row&7 unchanged).
+// walks rows in +16 steps = +4096 bytes, which commutes with the bits-4..7
+// row swizzle (it reads row & 15 only); rbase+4 changes it, hence the second
+// address register.  The addresses are ff_map_tr (fa32_lds_map.h).
 // `l15` is the lane id mod 16: only its bits 0-3 are read (bit 4 comes in
 // through l31, bit 5 through half), so lane or tid may be passed unmasked.
 DEV void ff_tr_read8(const unsigned short* tile, int ds, int l15, int l31, int half,
                      ff_shortx4 (&t)[4][2]) {
-  const int col2 = (ds * 32 + (l31 & 16) + (l15 & 3) * 4) * 2;
-  const int row0 = half * 8 + ((l15 & 15) >> 2);  // tile row, jj = 0
-  const int a0 = (row0 * 256 + col2) ^ ((row0 & 7) << 4);
-  const int row1 = row0 + 4;                       // jj = 1
-  const int a1 = (row1 * 256 + col2) ^ ((row1 & 7) << 4);
+  static_assert(FF_MAP_KS_BYTES == 4096, "the offset: immediates below step 16 rows");
+  const int a0 = ff_map_tr(ds, l15, l31, half, 0);  // tile rows half*8 + 0..3
+  const int a1 = ff_map_tr(ds, l15, l31, half, 1);  // tile rows half*8 + 4..7
   ff_lds_p b0 = (ff_lds_p)((const char*)tile + a0);
   ff_lds_p b1 = (ff_lds_p)((const char*)tile + a1);
   // ONE asm statement for all 8 reads + the drain: with separate
