@@ -129,7 +129,11 @@ fa2_dq_bf16(const unsigned short* __restrict__ q,
   __shared__ unsigned short ldo[FB_TILE * FB_D];  // block's dO q rows (swz)
 
   const ff_ctx c = ff_prologue(Hq, Hkv, S);
-  const int tid = c.tid, wave = c.wave, l31 = c.l31, half = c.half;
+  const int tid = c.tid, l31 = c.l31, half = c.half;
+  // The wave index in a scalar register: `active` and `need_mask` below are
+  // then scalar compares and branches, and the epilogue rebuilds its row from
+  // it (see there).
+  const int wave = __builtin_amdgcn_readfirstlane(c.wave);
   // Tile t costs t + 1 units of work and the hardware dispatches blocks in
   // grid order: walk a head's tiles from the last (heaviest) one down, so the
   // blocks that start last are the cheap ones and the kernel's tail is short
@@ -190,19 +194,19 @@ fa2_dq_bf16(const unsigned short* __restrict__ q,
           ff_shortx8 dof = ff_bfrag(ldo, wave * FB_OWN + l31, ks, half);
           dp[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr, dof, dp[s2], 0, 0, 0);
         }
-      // dS' = P' * (dP' - delta); P' = exp2(st*scale2 - lse2); mask kv > q
+      // mask kv > q: only a diagonal tile (wave-uniform need_mask, 4 of a
+      // block's tiles) pays for it
+      if (need_mask) ff_mask<true>(st, my_q - kv0 - 4 * half);
+      // dS' = P' * (dP' - delta); P' = exp2(st*scale2 - lse2)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          int kv = ff_drow(kv0 + s2 * 32, r, half);
-          float x = st[s2][r] * scale2 - lse2;
-          if (need_mask && kv > my_q) x = -INFINITY;
-          float p = __builtin_amdgcn_exp2f(x);
+          float p = __builtin_amdgcn_exp2f(st[s2][r] * scale2 - lse2);
           st[s2][r] = p * (dp[s2][r] - dlt);
         }
       ff_shortx8 pb[4];
-      ff_relayout(st, pb, half);  // B-frags [q][kv-contraction]
+      ff_relayout(st, pb);  // B-frags [q][kv-contraction]
       // dQacc[d][q] += K^T . dS' (fwd's PV shape: A via tr, B = relayout)
 #pragma unroll
       for (int ds = 0; ds < 4; ++ds) {
@@ -216,8 +220,19 @@ fa2_dq_bf16(const unsigned short* __restrict__ q,
     }
   }
 
-  // epilogue: dQ[q][d] = scale * acc (D-layout: rows = d, col = q = l31)
-  ff_store_row(dq + qbase + (int64_t)my_q * FB_D, dqacc, scale, half);
+  // epilogue: dQ[q][d] = scale * acc (D-layout: rows = d, col = q = l31).
+  // The row address and `half` are worked out again here, from the scalar
+  // wave index and a lane id read afresh (volatile, so it stays below the
+  // loop): otherwise the compiler keeps them in three VGPRs across the tile
+  // loop, which has none to spare, and spills them to scratch (16 B/lane).
+  // This steers the register allocator of one compiler: tests/
+  // test_fa32_resources.py (scratch 0, <= 256 VGPRs) is what says when it no
+  // longer suffices, and building without it under that test, when it is no
+  // longer needed.
+  int elane;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(elane));
+  const int e_q = qt * FB_TILE + wave * FB_OWN + (elane & 31);
+  ff_store_row(dq + qbase + (int64_t)e_q * FB_D, dqacc, scale, elane >> 5);
 }
 
 // ---------------------------------------------------------------------------
@@ -294,32 +309,54 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
         st[s2] = (ff_floatx16)(0.f);
         if constexpr (DK) dp[s2] = (ff_floatx16)(0.f);
       }
+      if constexpr (!DK) {
+        // dv has the registers (186 of 256) to read its 16 row fragments 4
+        // MFMAs ahead: left alone the compiler reads one or two, waits and
+        // multiplies, a full LDS round trip per pair of MFMAs.  The two
+        // accumulator chains alternate; each chain's ks order, and so every
+        // bit, is unchanged.  The group barriers pin the order: 4 reads, then
+        // 12 x (MFMA, read), then the last 4 MFMAs (0x100 = DS read, 0x008 =
+        // MFMA).  2.65 -> 2.50 ms per call at the bench shape; dk (254 VGPRs)
+        // has no room for it.
+        ff_shortx8 qfr[16];
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
+        for (int i = 0; i < 16; ++i) qfr[i] = ff_afrag(lq, i & 1, i >> 1, l31, half);
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-          ff_shortx8 qfr = ff_afrag(lq, s2, ks, l31, half);
-          st[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr, kf[ks], st[s2], 0, 0, 0);
-          if constexpr (DK) {
+        for (int i = 0; i < 16; ++i)
+          st[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr[i], kf[i >> 1], st[i & 1], 0, 0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+      } else {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+          for (int ks = 0; ks < 8; ++ks) {
+            ff_shortx8 qfr = ff_afrag(lq, s2, ks, l31, half);
+            st[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr, kf[ks], st[s2], 0, 0, 0);
             ff_shortx8 dofr = ff_afrag(ldo, s2, ks, l31, half);
             dp[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dofr, vf[ks], dp[s2], 0, 0, 0);
           }
-        }
-      // P = exp2(st*scale2 - lse2[q row]); mask q < kv (broadcast reads);
+      }
+      // mask q < kv: only a diagonal tile (wave-uniform need_mask) pays for it
+      if (need_mask) ff_mask<false>(st, my_kv - qt0 - 4 * half);
+      // P = exp2(st*scale2 - lse2[q row]) (broadcast reads);
       // dk: dS = P * (dP - delta[q row])
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           int qrow = ff_drow(s2 * 32, r, half);
-          float x = st[s2][r] * scale2 - llse[qrow];
-          if (need_mask && qt0 + qrow < my_kv) x = -INFINITY;
-          float p = __builtin_amdgcn_exp2f(x);
+          float p = __builtin_amdgcn_exp2f(st[s2][r] * scale2 - llse[qrow]);
           if constexpr (DK) st[s2][r] = p * (dp[s2][r] - ldelta[qrow]);
           else st[s2][r] = p;
         }
       ff_shortx8 pb[4];
-      ff_relayout(st, pb, half);  // B-frags [kv][q-contraction]
+      ff_relayout(st, pb);  // B-frags [kv][q-contraction]
       // dv: acc[d][kv] += dO^T . P   |   dk: acc[d][kv] += Q^T . dS
       // (A via tr reads of dO | Q)
 #pragma unroll
@@ -478,7 +515,9 @@ fa2_dvdk_bf16(const unsigned short* __restrict__ q,
           ff_shortx8 dofr = ff_afrag(ldo, s2, ks, l31, half);
           dp[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dofr, vfr, dp[s2], 0, 0, 0);
         }
-      // P = exp2(st*scale2 - lse2[q row]) in place (mask q < kv)
+      // mask q < kv on the diagonal tiles only, as fa2_dv / fa2_dk do
+      if (need_mask) ff_mask<false>(st, my_kv - qt0 - 4 * half);
+      // P = exp2(st*scale2 - lse2[q row]) in place
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
@@ -486,14 +525,12 @@ fa2_dvdk_bf16(const unsigned short* __restrict__ q,
           int qrow = ff_drow(s2 * 32, r, half);
           float l2 = __int_as_float(
               __builtin_amdgcn_ds_bpermute(qrow * 4, __float_as_int(lse_reg)));
-          float x = st[s2][r] * scale2 - l2;
-          if (need_mask && qt0 + qrow < my_kv) x = -INFINITY;
-          st[s2][r] = __builtin_amdgcn_exp2f(x);
+          st[s2][r] = __builtin_amdgcn_exp2f(st[s2][r] * scale2 - l2);
         }
       // dV phase: dVacc[d][kv] += dO^T . P
       {
         ff_shortx8 pb[4];
-        ff_relayout(st, pb, half);  // B-frags [kv][q-contraction]
+        ff_relayout(st, pb);  // B-frags [kv][q-contraction]
 #pragma unroll
         for (int ds = 0; ds < 4; ++ds) {
           ff_shortx4 t[4][2];
@@ -516,7 +553,7 @@ fa2_dvdk_bf16(const unsigned short* __restrict__ q,
         }
       {
         ff_shortx8 pb[4];
-        ff_relayout(st, pb, half);  // B-frags [kv][q-contraction]
+        ff_relayout(st, pb);  // B-frags [kv][q-contraction]
         // dKacc[d][kv] += Q^T . dS
 #pragma unroll
         for (int ds = 0; ds < 4; ++ds) {

@@ -99,6 +99,18 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
     ff_chunk_store(kreg[j], lk[0], e);
     ff_chunk_store(vreg[j], lv[0], e);
   }
+  // Retire every vector load here (s_waitcnt vmcnt(0); expcnt and lgkmcnt
+  // fields left at "no wait").  The compiler schedules the 8 Q-fragment loads
+  // after the tile-0 K/V loads and waits only for the latter before this
+  // barrier, so its scoreboard enters the loop with 8 loads pending and it
+  // puts vmcnt(7)..vmcnt(0) in front of the QK^T MFMAs that read qf[0..7] in
+  // EVERY iteration.  From the second tile on those counts no longer cover Q
+  // but the 8 K/V prefetch loads issued just above them, and the wave stalls
+  // on the prefetch that the double buffer exists to carry across softmax and
+  // PV.  With the scoreboard clean the loop's only vmcnt wait is in front of
+  // the staging stores after PV.  (A builtin, not inline asm: the wait-count
+  // pass does not look inside an asm statement.)
+  __builtin_amdgcn_s_waitcnt(0x0F70);
   __syncthreads();
 
   for (int jkv = 0; jkv < last_kv; ++jkv) {
@@ -208,7 +220,7 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
     } else {
     // ---- P relayout to PV B-operand (4 ksteps of 16 kv, KV=64) ----
     ff_shortx8 pb[4];
-    ff_relayout(st, pb, half);
+    ff_relayout(st, pb);
     // ---- PV: O[d][q] += V^T . P  (contraction kv; A-frag V^T rows
     // d = ds*32 + l31 via tr reads of the V tile) ----
 #pragma unroll

@@ -612,6 +612,10 @@ std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Te
   TORCH_CHECK(!(bshd && fused_dvdk), "fa_bwd2: the fused dv+dk kernel reads [B,Hq,S,D] ",
               "only: bshd=True needs fused_dvdk=False");
   FaShape s = fa_check(b, FB_TILE, q, k, v, o, dout, lse, bshd);
+  // the kernels write -inf into the masked scores BEFORE scaling them
+  // (ff_mask): only a positive finite scale keeps them -inf
+  TORCH_CHECK(scale > 0 && std::isfinite(scale), b.fn, ": scale = ", scale,
+              " must be positive and finite");
   auto delta = fa_bwd_delta(b, s, dout, o, bshd);
   auto dq = at::empty_like(q);
   dim3 grid(s.S / FB_TILE, s.Hq, s.B);
@@ -871,6 +875,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("permlane_probe", &permlane_probe);
   m.def("mfma32_probe", &mfma32_probe);
   m.def("tr_probe", &tr_probe);
+  m.def("_relayout_probe", &relayout_probe, pybind11::arg("x"));
   m.def("philox_uniform_", &philox_fill<false>);
   m.def("philox_normal_", &philox_fill<true>);
   m.def("philox_dropout", &philox_dropout);

@@ -164,41 +164,70 @@ DEV void ff_row_frags(const unsigned short* __restrict__ row, ff_shortx8 (&f)[8]
 // Relayout a D-layout [rows][cols=l31] fp32 register block (2 subtiles of 32
 // rows) into 4 B-operand fragments with lane-dim = former cols and
 // contraction = former rows, in-register: v_cvt_pk_bf16_f32 pairs +
-// permlane32_swap (guide T12: one swap fills both half-row words; no LDS
-// round trip, no divergent branch).
+// two-operand permlane32_swap (guide T12: one swap fills both half-row words;
+// no LDS round trip, no select, no divergent branch).
 // Derivation (regs r: row_local = ff_drow(0, r, half)):
 //   group g (16 rows): own regs g*8+0..3 -> row g*16 + (0..3)+4*half ("LO")
 //                      own regs g*8+4..7 -> row g*16 + (8..11)+4*half ("HI")
 //   B-frag wants row = g*16 + half*8 + e:
 //     half=0: e0-3 = own LO, e4-7 = partner LO (their +4..7)
 //     half=1: e0-3 = partner HI (their 8..11), e4-7 = own HI (12..15)
-DEV void ff_relayout(const ff_floatx16 st[2], ff_shortx8 pb[4], int half) {
+//   permlane32_swap(LO, HI) (result layout: ff_swap_other's comment) hands
+//     half=0: r0 = own LO,     r1 = partner LO
+//     half=1: r0 = partner HI, r1 = own HI
+//   so the fragment is {r0 of word 0, r0 of word 1, r1 of word 0, r1 of
+//   word 1} in BOTH halves: 2 swaps per 16-row group, 8 per tile.
+// ff_cvt_pk is the packed convert alone, so the relayout probe's reference
+// formulation (probes.hip) starts from the same words.
+DEV unsigned ff_cvt_pk(float a, float b) {
+  unsigned w;
+  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(a), "v"(b));
+  return w;
+}
+DEV void ff_relayout(const ff_floatx16 st[2], ff_shortx8 pb[4]) {
 #pragma unroll
   for (int s2 = 0; s2 < 2; ++s2) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      unsigned lo0, lo1, hi0, hi1;
-      asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo0)
-                   : "v"(st[s2][g * 8 + 0]), "v"(st[s2][g * 8 + 1]));
-      asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo1)
-                   : "v"(st[s2][g * 8 + 2]), "v"(st[s2][g * 8 + 3]));
-      asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi0)
-                   : "v"(st[s2][g * 8 + 4]), "v"(st[s2][g * 8 + 5]));
-      asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi1)
-                   : "v"(st[s2][g * 8 + 6]), "v"(st[s2][g * 8 + 7]));
-      int p0 = ff_swap_other((int)lo0, half);  // partner's LO word0
-      int p1 = ff_swap_other((int)lo1, half);  // partner's LO word1
-      int p2 = ff_swap_other((int)hi0, half);  // partner's HI word0
-      int p3 = ff_swap_other((int)hi1, half);  // partner's HI word1
-      ff_intx4 frag;
-      if (half == 0) {
-        frag = (ff_intx4){(int)lo0, (int)lo1, p0, p1};
-      } else {
-        frag = (ff_intx4){p2, p3, (int)hi0, (int)hi1};
-      }
+      const unsigned lo0 = ff_cvt_pk(st[s2][g * 8 + 0], st[s2][g * 8 + 1]);
+      const unsigned lo1 = ff_cvt_pk(st[s2][g * 8 + 2], st[s2][g * 8 + 3]);
+      const unsigned hi0 = ff_cvt_pk(st[s2][g * 8 + 4], st[s2][g * 8 + 5]);
+      const unsigned hi1 = ff_cvt_pk(st[s2][g * 8 + 6], st[s2][g * 8 + 7]);
+      auto w0 = __builtin_amdgcn_permlane32_swap(lo0, hi0, false, false);
+      auto w1 = __builtin_amdgcn_permlane32_swap(lo1, hi1, false, false);
+      ff_intx4 frag = (ff_intx4){(int)w0[0], (int)w1[0], (int)w0[1], (int)w1[1]};
       pb[s2 * 2 + g] = *reinterpret_cast<ff_shortx8*>(&frag);
     }
   }
+}
+
+// Causal mask of a D-layout 64-row tile, applied by the backward kernels on
+// their diagonal tiles only (a wave-uniform branch), as a pre-pass over the
+// raw scores: the masked registers of st become -inf, and the one exp2 / dS
+// body that every tile runs turns them into P = 0, dS = 0.
+// row = the element's tile row LESS this lane's 4*half, a compile-time
+// constant per register, so the mask is one compare of a constant against a
+// per-lane limit and no index arithmetic.
+//   ABOVE: rows > lim are masked (fa2_dq: kv > q);
+//   else : rows < lim are masked (fa2_dv / fa2_dk: q < kv).
+// Why -inf BEFORE the fma gives the bits that "x = -inf after it" gave: the
+// body computes x = fma(st, scale2, -lse2) with scale2 = scale * log2(e) > 0
+// (the fa_bwd2 binding refuses a scale that is not positive and finite; the
+// forward masks after scaling and takes any), so -inf * scale2 = -inf, and
+// lse2 is finite: an
+// active row always holds its own diagonal element, so its logsumexp is the
+// log of a positive sum, never -inf, and +inf or a finite value leaves
+// -inf - lse2 = -inf.  Then exp2(-inf) = +0 exactly as before.  (Only a NaN
+// lse, with which the row's gradients are NaN already, would differ.)
+template <bool ABOVE>
+DEV void ff_mask(ff_floatx16 (&st)[2], int lim) {
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = ff_drow(s2 * 32, r, 0);
+      if (ABOVE ? row > lim : row < lim) st[s2][r] = -INFINITY;
+    }
 }
 
 // 8 tr reads (4 ks x 2) of a TRANSPOSED A-operand from a swizzled 64x128

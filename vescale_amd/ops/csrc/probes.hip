@@ -1,5 +1,6 @@
 // Hardware layout probes and their bindings (decoded by tools/fa_fwd_check.py,
-// tools/permlane_probe.py, tools/tr_probe_check.py).  Included by extension.hip
+// tools/permlane_probe.py, tools/tr_probe_check.py; the relayout probe by
+// tests/test_fa32_tile_paths_gpu.py).  Included by extension.hip
 // after the host helpers (Binding); the device helpers it probes come from
 // fa32_common.h.
 #include "fa32_common.h"
@@ -67,6 +68,56 @@ extern "C" __global__ void tr_probe_kernel(unsigned short* out) {
   }
 }
 
+// ff_relayout's earlier formulation, kept for the relayout probe ONLY: every
+// packed word exchanged with the one-operand swap (ff_swap_other, which picks
+// the partner's copy with a select), the fragment then assembled with a second
+// select on `half`: 16 swaps and 32 selects per tile against ff_relayout's 8
+// swaps.  The probe holds ff_relayout to this one's bits.
+DEV void ff_relayout_ref(const ff_floatx16 st[2], ff_shortx8 pb[4], int half) {
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const unsigned lo0 = ff_cvt_pk(st[s2][g * 8 + 0], st[s2][g * 8 + 1]);
+      const unsigned lo1 = ff_cvt_pk(st[s2][g * 8 + 2], st[s2][g * 8 + 3]);
+      const unsigned hi0 = ff_cvt_pk(st[s2][g * 8 + 4], st[s2][g * 8 + 5]);
+      const unsigned hi1 = ff_cvt_pk(st[s2][g * 8 + 6], st[s2][g * 8 + 7]);
+      int p0 = ff_swap_other((int)lo0, half);  // partner's LO word0
+      int p1 = ff_swap_other((int)lo1, half);  // partner's LO word1
+      int p2 = ff_swap_other((int)hi0, half);  // partner's HI word0
+      int p3 = ff_swap_other((int)hi1, half);  // partner's HI word1
+      ff_intx4 frag;
+      if (half == 0) {
+        frag = (ff_intx4){(int)lo0, (int)lo1, p0, p1};
+      } else {
+        frag = (ff_intx4){p2, p3, (int)hi0, (int)hi1};
+      }
+      pb[s2 * 2 + g] = *reinterpret_cast<ff_shortx8*>(&frag);
+    }
+  }
+}
+
+// relayout probe: one wave; lane l reads its 2 x 16 fp32 D-layout registers
+// from in[l][32] and writes the 4 fragments of ff_relayout_ref to
+// out[0][l][4][8] and those of ff_relayout to out[1][l][4][8] (bf16 bits).
+extern "C" __global__ void relayout_probe_kernel(const float* __restrict__ in,
+                                                 unsigned short* __restrict__ out) {
+  const int lane = threadIdx.x;  // one wave
+  ff_floatx16 st[2];
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) st[s2][r] = in[lane * 32 + s2 * 16 + r];
+  ff_shortx8 ref[4], got[4];
+  ff_relayout_ref(st, ref, lane >> 5);
+  ff_relayout(st, got);
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    *reinterpret_cast<ff_shortx8*>(out + ((0 * 64 + lane) * 4 + f) * 8) = ref[f];
+    *reinterpret_cast<ff_shortx8*>(out + ((1 * 64 + lane) * 4 + f) * 8) = got[f];
+  }
+}
+
 namespace {
 
 at::Tensor probe_out(at::IntArrayRef sizes, at::ScalarType dtype) {
@@ -88,6 +139,15 @@ at::Tensor mfma32_probe() {
 at::Tensor tr_probe() {
   auto out = probe_out({4, 4, 64, 8}, at::kShort);
   Binding("tr_probe", "out", out).launch(tr_probe_kernel, 1, 64, bf16_mut(out));
+  return out;
+}
+
+// x: [64, 32] fp32 (lane, s2*16 + r) -> [2 (ref, new), 64, 4, 8] bf16 bits
+at::Tensor relayout_probe(at::Tensor x) {
+  Binding b("_relayout_probe", "x", x);
+  b.arg("x", x, F32, {64, 32});
+  auto out = at::empty({2, 64, 4, 8}, x.options().dtype(at::kShort));  // on x's device
+  b.launch(relayout_probe_kernel, 1, 64, x.data_ptr<float>(), bf16_mut(out));
   return out;
 }
 
