@@ -6,6 +6,7 @@ vescale_amd.moe.parallelize_experts (token all-to-all over xGMI).
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import List
 
@@ -15,7 +16,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..moe._utils import global_all_to_all_single
-from ..ops import build_rope_table, fused_cross_entropy, rmsnorm, rope_qkv, swiglu_packed
+from ..ops import (build_rope_table, fused_cross_entropy, grouped_fits, grouped_linear, rmsnorm,
+                   rope_qkv, swiglu_packed)
 from .llama import Attention, LlamaConfig, RMSNorm
 
 
@@ -49,6 +51,25 @@ class Expert(nn.Module):
 
     def forward(self, x):
         return self.w2(swiglu_packed(self.w13(x)))
+
+
+# VESCALE_MOE_GEMM selects how the expert FFNs of a MoELayer run:
+#   "loop"     — a Python loop over the experts, two library GEMMs each, sized
+#                by routed counts the host waits for.
+#   "grouped"  — grouped_linear(w13) -> swiglu_packed -> grouped_linear(w2):
+#                one HIP launch per GEMM over all experts, offsets read on the
+#                device (ops/csrc/gemm_grouped.hip); the dense path then has
+#                no host sync between router and combine.
+# Shapes outside the grouped kernels' contract (ops.grouped_fits) always take
+# the loop.  The default follows the A/B in profiles/moe_grouped_ab.txt.
+MOE_GEMM_DEFAULT = "loop"
+
+
+def _moe_gemm_backend() -> str:
+    backend = os.environ.get("VESCALE_MOE_GEMM", MOE_GEMM_DEFAULT)
+    if backend not in ("grouped", "loop"):
+        raise ValueError(f"VESCALE_MOE_GEMM = {backend!r} must be 'grouped' or 'loop'")
+    return backend
 
 
 class MoELayer(nn.Module):
@@ -92,21 +113,45 @@ class MoELayer(nn.Module):
             out = self._ep_moe(xt, weights, ids)
         return out.reshape(B, S, D)
 
+    def _grouped(self, x, expert_ids) -> bool:
+        """The grouped kernels serve these experts on these rows."""
+        if _moe_gemm_backend() != "grouped" or not len(expert_ids):
+            return False
+        w13 = [self.experts[e].w13.weight for e in expert_ids]
+        w2 = [self.experts[e].w2.weight for e in expert_ids]
+        return grouped_fits(x, w13) and grouped_fits(x.new_empty(0, w2[0].shape[1]), w2)
+
+    def _grouped_ffn(self, sorted_x, offs, expert_ids):
+        """Expert FFN of rows sorted by expert; offs int32 [len(expert_ids) + 1]
+        on the device.  The weights stay the experts' own parameters."""
+        w13 = [self.experts[e].w13.weight for e in expert_ids]
+        w2 = [self.experts[e].w2.weight for e in expert_ids]
+        return grouped_linear(swiglu_packed(grouped_linear(sorted_x, w13, offs)), w2, offs)
+
     def _dense_moe(self, xt, weights, ids):
         T, D = xt.shape
         k = self.cfg.top_k
+        E = self.cfg.n_experts
         flat_ids = ids.reshape(-1)          # [T*k]
-        flat_x = xt.repeat_interleave(k, dim=0)
         order = torch.argsort(flat_ids, stable=True)
-        counts = torch.bincount(flat_ids, minlength=self.cfg.n_experts)
-        sorted_x = flat_x[order]
-        outs = torch.empty_like(sorted_x)
-        off = 0
-        for e in range(self.cfg.n_experts):
-            n = int(counts[e])
-            if n:
-                outs[off : off + n] = self.experts[e](sorted_x[off : off + n])
-            off += n
+        if self._grouped(xt, range(E)):
+            # offs[e] = rows routed below expert e = cumsum(bincount) with a
+            # leading 0, computed without bincount's host sync; sorted row i
+            # is token order[i] // k, gathered without the k-fold copy of x
+            offs = torch.searchsorted(
+                flat_ids[order], torch.arange(E + 1, device=flat_ids.device)).to(torch.int32)
+            sorted_x = xt[torch.div(order, k, rounding_mode="floor")]
+            outs = self._grouped_ffn(sorted_x, offs, range(E))
+        else:
+            sorted_x = xt.repeat_interleave(k, dim=0)[order]
+            counts = torch.bincount(flat_ids, minlength=E)
+            outs = torch.empty_like(sorted_x)
+            off = 0
+            for e in range(E):
+                n = int(counts[e])
+                if n:
+                    outs[off : off + n] = self.experts[e](sorted_x[off : off + n])
+                off += n
         inv = torch.empty_like(order)
         inv[order] = torch.arange(order.numel(), device=order.device)
         unsorted = outs[inv].reshape(T, k, D)
@@ -146,13 +191,19 @@ class MoELayer(nn.Module):
             rei = torch.zeros(0, dtype=torch.int64, device=recv.device)
         order2 = torch.argsort(rei, stable=True)
         grouped = recv[order2]
-        outs = torch.empty_like(grouped)
-        off = 0
-        for e in self.local_expert_ids:
-            n = int(sum(int(recv_counts[r * E + e]) for r in range(W)))
-            if n:
-                outs[off : off + n] = self.experts[e](grouped[off : off + n])
-            off += n
+        local_n = [int(sum(int(recv_counts[r * E + e]) for r in range(W)))
+                   for e in self.local_expert_ids]
+        if self._grouped(grouped, self.local_expert_ids):
+            # the counts are on the host already (the all-to-all needed them)
+            offs = torch.tensor([0] + local_n, dtype=torch.int32).cumsum(0, dtype=torch.int32)
+            outs = self._grouped_ffn(grouped, offs.to(grouped.device), self.local_expert_ids)
+        else:
+            outs = torch.empty_like(grouped)
+            off = 0
+            for e, n in zip(self.local_expert_ids, local_n):
+                if n:
+                    outs[off : off + n] = self.experts[e](grouped[off : off + n])
+                off += n
         inv2 = torch.empty_like(order2)
         inv2[order2] = torch.arange(order2.numel(), device=order2.device)
         back = outs[inv2]

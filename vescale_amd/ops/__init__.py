@@ -55,4 +55,6 @@ from .functional import (  # noqa: E402,F401
     l2norm_sq,
     scale_flat_,
     linear,
+    grouped_linear,
+    grouped_fits,
 )

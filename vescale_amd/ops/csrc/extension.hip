@@ -19,12 +19,15 @@
 #include "philox_random.hip"
 #include "gemm.hip"
 #include "gemm8.hip"
+#include "gemm_grouped.hip"
 #include "attention_fwd.hip"
 #include "attention_bwd2.hip"
 #include "attention_gen.hip"
 
 #include <climits>
 #include <sstream>
+#include <string>
+#include <variant>
 #include <vector>
 
 namespace {
@@ -501,10 +504,96 @@ at::Tensor gemm_tn(at::Tensor a, at::Tensor b, int64_t variant) {
   return c;
 }
 
-at::Tensor gemm_tn8(at::Tensor a, at::Tensor b, int64_t mode) {
-  // via the 8-phase 256x256 template (gemm8.hip)
+// ------------------------------ grouped expert GEMM ------------------------
+// The grouped forms of gemm_tn8 (gemm_grouped.hip), selected by group_form:
+//   "fwd"    a = X  [T,K]                  -> Y  [T,N]
+//   "dgrad"  a = dY [T,N]                  -> dX [T,K]
+//   "wgrad"  a = dY [T,N], group_x X [T,K] -> dW [E,N,K]
+// ws: the E expert weights, each [N,K], as a list of tensors (their base
+// pointers travel in the kernel arguments; nothing is stacked) or as one
+// [E,N,K] tensor.  group_offsets: int32 [E+1] on the device; its VALUES are
+// not read here (that would need a sync), the kernels clamp them.  group_out:
+// an optional preallocated result.  Rows outside the groups are not written.
+using Weights = std::variant<at::Tensor, std::vector<at::Tensor>>;
+
+void gemm_grouped_aligned(const Binding& b, const char* name, const at::Tensor& t) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0, b.fn,
+              ": argument '", name, "' must be 16-byte aligned");
+}
+
+at::Tensor gemm_grouped(const Binding& b, const at::Tensor& a, const Weights& ws,
+                        const OptTensor& offs, const std::string& form,
+                        const OptTensor& x, const OptTensor& out_arg) {
+  const bool fwd = form == "fwd", dgrad = form == "dgrad", wgrad = form == "wgrad";
+  TORCH_CHECK(fwd || dgrad || wgrad, b.fn, ": group_form = '", form,
+              "' must be 'fwd', 'dgrad' or 'wgrad'");
+  TORCH_CHECK(offs.has_value(), b.fn, ": group_form = '", form, "' needs group_offsets");
+  TORCH_CHECK(wgrad == x.has_value(), b.fn, ": group_x is the X of group_form = 'wgrad' ",
+              "and of no other form");
+  const auto* list = std::get_if<std::vector<at::Tensor>>(&ws);
+  const at::Tensor* stacked = std::get_if<at::Tensor>(&ws);
+  TORCH_CHECK(list || stacked->dim() == 3, b.fn,
+              ": b must be a list of [N,K] tensors or one [E,N,K] tensor, got sizes=",
+              stacked->sizes());
+  const int64_t E = list ? (int64_t)list->size() : stacked->size(0);
+  TORCH_CHECK(E >= 1 && E <= GG_MAX_E, b.fn, ": E = ", E, " experts must be in 1..", GG_MAX_E);
+  const at::Tensor& w0 = list ? (*list)[0] : *stacked;
+  TORCH_CHECK(w0.dim() >= 2, b.fn, ": b[0] must be [N,K], got sizes=", w0.sizes());
+  const int64_t N = w0.size(-2), K = w0.size(-1), T = a.dim() == 2 ? a.size(0) : -1;
+  TORCH_CHECK(K > 0 && K % GG_BN == 0, b.fn, ": K = ", K, " must be a positive multiple of ",
+              GG_BN);
+  TORCH_CHECK(N > 0 && N % GG_BN == 0, b.fn, ": N = ", N, " must be a positive multiple of ",
+              GG_BN);
+  TORCH_CHECK(N * K <= INT_MAX, b.fn, ": N * K = ", N * K, " must fit int");
+  b.arg("a", a, BF16, {-1, fwd ? K : N});
+  TORCH_CHECK(T <= INT_MAX - 2 * GG_BM, b.fn, ": T = ", T, " rows must fit int");
+  b.arg("group_offsets", offs, I32, {E + 1});
+  b.arg("group_x", x, BF16, {T, K});
+  gemm_grouped_aligned(b, "a", a);
+  if (wgrad) gemm_grouped_aligned(b, "group_x", *x);
+  GGPtrs tab{};
+  if (list) {
+    for (int64_t e = 0; e < E; ++e) {
+      const std::string name = "b[" + std::to_string(e) + "]";
+      b.arg(name.c_str(), (*list)[e], BF16, {N, K});
+      gemm_grouped_aligned(b, name.c_str(), (*list)[e]);
+      tab.p[e] = bf16((*list)[e]);
+    }
+  } else {
+    b.arg("b", *stacked, BF16, {E, N, K});
+    gemm_grouped_aligned(b, "b", *stacked);
+    for (int64_t e = 0; e < E; ++e) tab.p[e] = bf16(*stacked) + e * N * K;
+  }
+  const at::DimVector osz = wgrad ? at::DimVector{E, N, K} : at::DimVector{T, fwd ? N : K};
+  b.arg("group_out", out_arg, BF16, at::IntArrayRef(osz));
+  at::Tensor out = out_arg.has_value() ? *out_arg : at::empty(osz, a.options());
+  gemm_grouped_aligned(b, "group_out", out);
+  if (T == 0) return wgrad ? out.zero_() : out;
+  const int* po = offs->data_ptr<int>();
+  if (wgrad) {
+    b.launch(gemm_grouped_wgrad_bf16, dim3((unsigned)(K / GG_BN), (unsigned)(N / GG_BM), (unsigned)E),
+             GG_THREADS, bf16(a), bf16(*x), po, bf16_mut(out), (int)T, (int)N, (int)K);
+  } else {
+    // T/128 + E row tiles >= sum over experts of ceil(rows / 128): no sync
+    dim3 grid((unsigned)(T / GG_BM + E), (unsigned)((fwd ? N : K) / GG_BN), 1);
+    b.launch(fwd ? gemm_grouped_rows_bf16<false> : gemm_grouped_rows_bf16<true>, grid,
+             GG_THREADS, bf16(a), tab, po, bf16_mut(out), (int)T, (int)E, (int)N, (int)K);
+  }
+  return out;
+}
+
+at::Tensor gemm_tn8(at::Tensor a, Weights bw, int64_t mode, OptTensor group_offsets,
+                    std::string group_form, OptTensor group_x, OptTensor group_out) {
+  // via the 8-phase 256x256 template (gemm8.hip); with group_form, the
+  // grouped expert forms (gemm_grouped.hip)
   Binding bd("gemm_tn8", "a", a);
   TORCH_CHECK(mode >= 0 && mode <= 8, "gemm_tn8: mode = ", mode, " must be in 0..8");
+  if (!group_form.empty() || group_offsets.has_value() || group_x.has_value() ||
+      group_out.has_value())
+    return gemm_grouped(bd, a, bw, group_offsets, group_form, group_x, group_out);
+  TORCH_CHECK(std::holds_alternative<at::Tensor>(bw),
+              "gemm_tn8: b is a list of tensors only with group_form");
+  const at::Tensor& b = std::get<at::Tensor>(bw);
   gemm_check(bd, a, b, G8_BM, G8_BN, G8_BK);
   int64_t M = a.size(0), K = a.size(1), N = b.size(0);
   TORCH_CHECK(mode != 5 || (K / 64) % 2 == 0, "mode 5 needs K % 128 == 0");
@@ -854,7 +943,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("l2norm_sq", &l2norm_sq);
   m.def("scale_", &scale_);
   m.def("gemm_tn", &gemm_tn, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("variant") = 0);
-  m.def("gemm_tn8", &gemm_tn8, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("mode") = 0);
+  m.def("gemm_tn8", &gemm_tn8, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("mode") = 0,
+        pybind11::arg("group_offsets") = pybind11::none(), pybind11::arg("group_form") = "",
+        pybind11::arg("group_x") = pybind11::none(), pybind11::arg("group_out") = pybind11::none());
   m.def("fa_bwd", &fa_bwd);
   m.def("fa_bwd2", &fa_bwd2, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
         pybind11::arg("o"), pybind11::arg("dout"), pybind11::arg("lse"),

@@ -838,8 +838,11 @@ def scale_flat_(x: torch.Tensor, scale) -> None:
 #   "gemm8"            — the in-tree 256x256 8-phase MFMA kernel
 #                        (ops/csrc/gemm8.hip, rot3np schedule) for the
 #                        forward and dgrad GEMMs; wgrad (both operands
-#                        contraction-major) stays on the library until the
-#                        tr-read wgrad kernel lands.  Honest A/B:
+#                        contraction-major) stays on the library: the
+#                        contraction-major kernels that exist now are the
+#                        grouped expert forms below (gemm_grouped.hip, dgrad
+#                        and wgrad staged transposed into LDS), which serve
+#                        grouped_linear, not this dense path.  Honest A/B:
 #                        profiles/gemm8_variants_ab_r2.log — the in-tree
 #                        kernel is ~75% of hipBLASLt on Llama shapes, so
 #                        blaslt remains the default (VERDICT r1 item 1:
@@ -897,3 +900,90 @@ def linear(x: torch.Tensor, w: torch.Tensor,
     if _gemm_backend() == "gemm8" and bias is None:
         return _Linear8.apply(x, w)
     return torch.nn.functional.linear(x, w, bias)
+
+
+# ---------------------------------------------------------------------------
+# Grouped expert linear (MoE): one launch per GEMM over all experts
+# ---------------------------------------------------------------------------
+GROUPED_MAX_EXPERTS = 64
+
+
+def _weight_list(weights):
+    """A stacked [E,N,K] tensor or a sequence of E [N,K] tensors -> (list of
+    the tensors the kernels read, stacked?)."""
+    if isinstance(weights, torch.Tensor):
+        return [weights], True
+    return list(weights), False
+
+
+def grouped_fits(x: torch.Tensor, weights) -> bool:
+    """The shape contract of the grouped kernels: bf16 on the GPU, 1..64
+    experts, N and K multiples of 128."""
+    ws, stacked = _weight_list(weights)
+    if not ws or (stacked and ws[0].dim() != 3):
+        return False
+    n_exp = ws[0].shape[0] if stacked else len(ws)
+    n, k = ws[0].shape[-2:]
+    return (
+        _use_hip(x, *ws)
+        and x.dtype == torch.bfloat16
+        and all(w.dtype == torch.bfloat16 for w in ws)
+        and 1 <= n_exp <= GROUPED_MAX_EXPERTS
+        and n % 128 == 0
+        and k % 128 == 0
+        and x.dim() == 2
+        and x.shape[1] == k
+    )
+
+
+class _GroupedLinear(torch.autograd.Function):
+    """The three grouped forms of gemm_tn8.  Weights stay separate tensors:
+    the binding reads their base pointers, nothing is stacked per step, and
+    wgrad's one [E,N,K] buffer is handed back as its slices."""
+
+    @staticmethod
+    def forward(ctx, x, offs, stacked, *ws):
+        x = x.contiguous()
+        ws = [w.contiguous() for w in ws]
+        ctx.save_for_backward(x, offs, *ws)
+        ctx.stacked = stacked
+        return _ext().gemm_tn8(x, ws[0] if stacked else ws, 0, group_offsets=offs,
+                               group_form="fwd")
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, offs, *ws = ctx.saved_tensors
+        b = ws[0] if ctx.stacked else ws
+        dy = dy.contiguous()
+        dx = dws = None
+        if ctx.needs_input_grad[0]:
+            dx = _ext().gemm_tn8(dy, b, 0, group_offsets=offs, group_form="dgrad")
+        if any(ctx.needs_input_grad[3:]):
+            dw = _ext().gemm_tn8(dy, b, 0, group_offsets=offs, group_form="wgrad", group_x=x)
+            dws = (dw,) if ctx.stacked else dw.unbind(0)
+        else:
+            dws = (None,) * len(ws)
+        return (dx, None, None, *dws)
+
+
+def grouped_linear(x: torch.Tensor, weights, group_offsets: torch.Tensor) -> torch.Tensor:
+    """y[t] = x[t] @ weights[e(t)]^T for rows sorted by expert.
+
+    x [T,K]; weights: E tensors [N,K] or one [E,N,K]; group_offsets [E+1]
+    (int32 on the HIP path): expert e owns rows offs[e]..offs[e+1], offs[0] = 0
+    and offs[E] = T.  bf16 on the GPU inside the shape contract
+    (`grouped_fits`) is one HIP launch per GEMM, forward and backward, with
+    no host sync; everything else is a per-group loop that reads the offsets
+    on the host."""
+    ws, stacked = _weight_list(weights)
+    if grouped_fits(x, weights):
+        offs = group_offsets.to(torch.int32).contiguous()
+        return _GroupedLinear.apply(x, offs, stacked, *ws)
+    bounds = group_offsets.tolist()
+    mats = ws[0].unbind(0) if stacked else ws
+    out = x.new_zeros(x.shape[0], mats[0].shape[0])
+    for e, w in enumerate(mats):
+        lo, hi = bounds[e], bounds[e + 1]
+        if hi > lo:
+            out[lo:hi] = torch.nn.functional.linear(x[lo:hi], w)
+    return out
