@@ -21,7 +21,9 @@ import subprocess
 import sys
 import tempfile
 
-KERNELS = ("fa_fwd_bf16", "fa2_dq_bf16", "fa2_dk_bf16", "fa2_dv_bf16", "fa2_dvdk_bf16")
+KERNELS = ("fa_fwd_bf16", "fa2_dq_bf16", "fa2_dk_bf16", "fa2_dv_bf16", "fa2_dvdk_bf16",
+           # the packed-document (SEG) instantiations; absent from builds before them
+           "fa_fwd_seg_bf16", "fa2_dq_seg_bf16", "fa2_dk_seg_bf16", "fa2_dv_seg_bf16")
 CLASSES = ("VALU", "v_exp", "v_cmp", "v_cndmask", "v_permlane32_swap", "ds_read", "ds_write",
            "MFMA", "s_waitcnt", "vmcnt", "s_barrier", "vmem")
 

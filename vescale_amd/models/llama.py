@@ -55,6 +55,11 @@ class LlamaConfig:
     # TP only: shard the LM head by vocab rows and fuse the class-sharded
     # loss (ops.vocab_parallel_cross_entropy); the embedding stays replicated
     vocab_parallel_head: bool = False
+    # packed documents only: promise that segment_ids marks documents as
+    # contiguous runs (an id that comes back later is a NEW document), which
+    # lets attention take the tuned D=128 kernels with their run mask
+    # (ops.flash_attention, contiguous_segments)
+    contiguous_segments: bool = False
 
     @property
     def head_dim(self) -> int:
@@ -142,8 +147,10 @@ class Attention(nn.Module):
             # falls back to SDPA off-GPU or for unsupported shapes
             o = flash_attention_causal(q, k, v)
         else:
-            # document mask: the general HIP kernel (its torch reference off-GPU)
-            o = flash_attention(q, k, v, is_causal=True, q_segment_ids=segment_ids)
+            # document mask: the general HIP kernel (its torch reference
+            # off-GPU); with cfg.contiguous_segments the tuned kernels' run mask
+            o = flash_attention(q, k, v, is_causal=True, q_segment_ids=segment_ids,
+                                contiguous_segments=cfg.contiguous_segments)
         o = o.transpose(1, 2).reshape(B, S, self.hq * cfg.head_dim)
         return reduce_from_tp(self.wo(o), self.tp)
 

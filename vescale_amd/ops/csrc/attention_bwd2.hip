@@ -30,6 +30,13 @@
 // fa_bwd_preprocess provides delta = rowsum(dO*O); dV/dK write per-Hq
 // partials and fa_bwd_reduce_gqa sums the GQA groups.
 //
+// Packed documents (fa2_dq_seg / fa2_dv_seg / fa2_dk_seg, template SEG): the
+// run bounds [B,2,S] of the forward's pre-pass.  dq keeps its row's start per
+// lane and begins at its block's first document; dv and dk keep their row's
+// end and stop at their block's last document; both apply the second bound
+// with ff_mask on boundary tiles only.  The kernels without the suffix are the
+// SEG=false instantiations; the fused fa2_dvdk has no SEG form.
+//
 // Reference parity: the reference framework uses the stock flash kernels;
 // this replaces the train step's heaviest kernel (the library backward is
 // 30% of the Llama-8B step — profiles/bench_kernel_stats_r1_final.txt).
@@ -115,15 +122,23 @@ fa_bwd_reduce_gqa(const unsigned short* __restrict__ part,  // [B,Hq,S,D]
 // ---------------------------------------------------------------------------
 // fa2_dq: dQ = scale * K^T-contract(dS'); grid (S/256, Hq, B)
 // ---------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
-fa2_dq_bf16(const unsigned short* __restrict__ q,
+// SEG: the packed-document mask (fa32_common.h), bounds [B,2,S]; null and
+// never read when !SEG.  Why the backward needs no dead-lane guard: the mask
+// keeps every row's own diagonal (start[i] <= i < end[i]), so the forward's
+// lse is the log of a positive sum, finite, and ff_mask's argument carries
+// over unchanged: a masked score is -inf before the fma, P = exp2(-inf - lse2)
+// = +0 and dS = 0 * (dP - delta) = 0, whether one element of a lane's tile is
+// masked or all of them.
+template <bool SEG>
+DEV void fa2_dq_t(const unsigned short* __restrict__ q,
             const unsigned short* __restrict__ k,
             const unsigned short* __restrict__ v,
             const unsigned short* __restrict__ dout,
             const float* __restrict__ lse,
             const float* __restrict__ delta,
             unsigned short* __restrict__ dq,
-            int B, int Hq, int Hkv, int S, float scale, int bshd) {
+            int B, int Hq, int Hkv, int S, float scale, int bshd,
+            const int* __restrict__ bounds) {
   __shared__ unsigned short lk[FB_OTH * FB_D];    // K kv-tile (swz)
   __shared__ unsigned short lv[FB_OTH * FB_D];    // V kv-tile (swz)
   __shared__ unsigned short ldo[FB_TILE * FB_D];  // block's dO q rows (swz)
@@ -167,10 +182,30 @@ fa2_dq_bf16(const unsigned short* __restrict__ q,
   const unsigned short* kg = k + kbase;
   const unsigned short* vg = v + kbase;
 
-  for (int jkv = 0; jkv < last_kv; ++jkv) {
+  // SEG, as in the forward: my_start per lane (mask my_start <= kv <= my_q),
+  // the wave's smallest and largest start from its first and last row, and the
+  // block's first kv tile from the block's first row, block-uniform and held
+  // to [0, last_kv] whatever bounds contains.
+  int my_start = 0, wstart_lo = 0, wstart_hi = 0, first_kv = 0;
+  if constexpr (SEG) {
+    const int* start = ff_seg_start(bounds, c.b, S);
+    my_start = start[my_q];
+    wstart_lo = __builtin_amdgcn_readfirstlane(my_start);
+    wstart_hi = __builtin_amdgcn_readlane(my_start, 31);
+    first_kv = ff_seg_tile(start[qt * FB_TILE] / FB_OTH, 0, last_kv);
+  }
+
+  for (int jkv = first_kv; jkv < last_kv; ++jkv) {
     const int kv0 = jkv * FB_OTH;
-    const bool active = (kv0 <= q0 + FB_OWN - 1);
+    bool active = (kv0 <= q0 + FB_OWN - 1);
     const bool need_mask = (kv0 + FB_OTH - 1 > q0);
+    // SEG: inactive while the tile lies before the wave's first document; the
+    // second bound is applied on the tiles that begin before its last one
+    bool need_seg = false;
+    if constexpr (SEG) {
+      active = active && (kv0 + FB_OTH - 1 >= wstart_lo);
+      need_seg = kv0 < wstart_hi;
+    }
     __syncthreads();  // previous tile's readers done
     ff_stage<FB_OTH, FB_THREADS>(kg + (int64_t)kv0 * FB_D, lk, tid);
     ff_stage<FB_OTH, FB_THREADS>(vg + (int64_t)kv0 * FB_D, lv, tid);
@@ -197,6 +232,9 @@ fa2_dq_bf16(const unsigned short* __restrict__ q,
       // mask kv > q: only a diagonal tile (wave-uniform need_mask, 4 of a
       // block's tiles) pays for it
       if (need_mask) ff_mask<true>(st, my_q - kv0 - 4 * half);
+      // SEG: mask kv < my_start, the same -inf pre-pass, boundary tiles only
+      if constexpr (SEG)
+        if (need_seg) ff_mask<false>(st, my_start - kv0 - 4 * half);
       // dS' = P' * (dP' - delta); P' = exp2(st*scale2 - lse2)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
@@ -235,6 +273,37 @@ fa2_dq_bf16(const unsigned short* __restrict__ q,
   ff_store_row(dq + qbase + (int64_t)e_q * FB_D, dqacc, scale, elane >> 5);
 }
 
+extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+fa2_dq_bf16(const unsigned short* __restrict__ q,
+            const unsigned short* __restrict__ k,
+            const unsigned short* __restrict__ v,
+            const unsigned short* __restrict__ dout,
+            const float* __restrict__ lse,
+            const float* __restrict__ delta,
+            unsigned short* __restrict__ dq,
+            int B, int Hq, int Hkv, int S, float scale, int bshd) {
+  fa2_dq_t<false>(q, k, v, dout, lse, delta, dq, B, Hq, Hkv, S, scale, bshd, nullptr);
+}
+// Resources of the SEG instantiations (hipcc -O3 --offload-arch=gfx950,
+// -Rpass-analysis=kernel-resource-usage), each equal to its SEG=false sibling
+// and at 2 waves/SIMD with scratch 0 and no spills:
+//   fa2_dq_seg_bf16  256 VGPRs, 0 AGPRs, 96 KiB LDS    (my_start is live across
+//                    the loop; the mask's second bound costs SGPRs, 83 -> 87)
+//   fa2_dv_seg_bf16  188 VGPRs, 0 AGPRs, 33024 B LDS
+//   fa2_dk_seg_bf16  254 VGPRs, 0 AGPRs, 33280 B LDS
+extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+fa2_dq_seg_bf16(const unsigned short* __restrict__ q,
+                const unsigned short* __restrict__ k,
+                const unsigned short* __restrict__ v,
+                const unsigned short* __restrict__ dout,
+                const float* __restrict__ lse,
+                const float* __restrict__ delta,
+                unsigned short* __restrict__ dq,
+                const int* __restrict__ bounds,
+                int B, int Hq, int Hkv, int S, float scale, int bshd) {
+  fa2_dq_t<true>(q, k, v, dout, lse, delta, dq, B, Hq, Hkv, S, scale, bshd, bounds);
+}
+
 // ---------------------------------------------------------------------------
 // fa2_dv / fa2_dk: one body, two instantiations; grid (S/256 kv-tiles, Hq, B),
 // per-Hq partials.
@@ -242,7 +311,10 @@ fa2_dq_bf16(const unsigned short* __restrict__ q,
 //             fragments, no dP MFMAs, no delta row in LDS)
 //   DK=true : dK[kv][d] = scale * sum_q dS Q, dS = P * (dP - delta)
 // ---------------------------------------------------------------------------
-template <bool DK>
+// SEG: dv and dk own kv rows, so a lane keeps my_end = end[b][my_kv] and the
+// mask is kv <= q < my_end; the q-tile loop ends at the block's last row's
+// document end (the block's maximum), not at S.
+template <bool DK, bool SEG>
 DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
                      const unsigned short* __restrict__ k,
                      const unsigned short* __restrict__ v,
@@ -250,7 +322,8 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
                      const float* __restrict__ lse,
                      const float* __restrict__ delta,
                      unsigned short* __restrict__ out_part,
-                     int Hq, int Hkv, int S, float scale, int bshd) {
+                     int Hq, int Hkv, int S, float scale, int bshd,
+                     const int* __restrict__ bounds) {
   __shared__ unsigned short lq[FB_OTH * FB_D];    // Q q-tile (swz)
   __shared__ unsigned short ldo[FB_OTH * FB_D];   // dO q-tile (swz)
   __shared__ float llse[FB_OTH];                  // q-tile rows' lse2
@@ -282,15 +355,36 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
   for (int i = 0; i < 4; ++i) acc[i] = (ff_floatx16)(0.f);
 
   const int jq0 = kvB / FB_OTH;       // diagonal q tile, block-uniform
-  const int n_jq = S / FB_OTH;
+  int n_jq = S / FB_OTH;
+  // SEG: end is monotone, so the wave's first row (lane 0) holds its smallest
+  // end, its last row (lane 31) the largest, and the block's last row the
+  // block's largest: one past the last q tile any of its rows is seen from,
+  // block-uniform and held to [jq0, S/64] whatever bounds contains.
+  int my_end = 0, wend_lo = 0, wend_hi = 0;
+  if constexpr (SEG) {
+    const int* end = ff_seg_end(bounds, c.b, S);
+    my_end = end[my_kv];
+    wend_lo = __builtin_amdgcn_readfirstlane(my_end);
+    wend_hi = __builtin_amdgcn_readlane(my_end, 31);
+    // ceil(end / 64), written without an overflow for any content
+    n_jq = ff_seg_tile(end[kvB + FB_TILE - 1] / FB_OTH + (end[kvB + FB_TILE - 1] % FB_OTH > 0),
+                       jq0, n_jq);
+  }
   const float* lseg = lse + c.rbase;
   const float* dltg = DK ? delta + c.rbase : nullptr;
   const ff_rows dorow = ff_o_rows(c, Hq, S, bshd);  // dout in either layout
 
   for (int jq = jq0; jq < n_jq; ++jq) {
     const int qt0 = jq * FB_OTH;
-    const bool active = (qt0 + FB_OTH - 1 >= kv0w);
+    bool active = (qt0 + FB_OTH - 1 >= kv0w);
     const bool need_mask = (qt0 < kv0w + FB_OWN - 1);
+    // SEG: inactive once the tile lies past the wave's last document; the
+    // second bound is applied on the tiles that reach the end of its first
+    bool need_seg = false;
+    if constexpr (SEG) {
+      active = active && (qt0 < wend_hi);
+      need_seg = qt0 + FB_OTH - 1 >= wend_lo;
+    }
     __syncthreads();
     ff_stage<FB_OTH, FB_THREADS>(q + qbase + (int64_t)qt0 * FB_D, lq, tid);
     ff_stage_rows<FB_OTH, FB_THREADS>(dout + dorow.base + (int64_t)qt0 * dorow.stride,
@@ -344,6 +438,9 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
       }
       // mask q < kv: only a diagonal tile (wave-uniform need_mask) pays for it
       if (need_mask) ff_mask<false>(st, my_kv - qt0 - 4 * half);
+      // SEG: mask q >= my_end, the same -inf pre-pass, boundary tiles only
+      if constexpr (SEG)
+        if (need_seg) ff_mask<true>(st, my_end - 1 - qt0 - 4 * half);
       // P = exp2(st*scale2 - lse2[q row]) (broadcast reads);
       // dk: dS = P * (dP - delta[q row])
 #pragma unroll
@@ -383,7 +480,19 @@ fa2_dv_bf16(const unsigned short* __restrict__ q,
             const float* __restrict__ lse,
             unsigned short* __restrict__ dv_part,
             int B, int Hq, int Hkv, int S, float scale, int bshd) {
-  fa2_dv_dk_t<false>(q, k, nullptr, dout, lse, nullptr, dv_part, Hq, Hkv, S, scale, bshd);
+  fa2_dv_dk_t<false, false>(q, k, nullptr, dout, lse, nullptr, dv_part, Hq, Hkv, S, scale, bshd,
+                            nullptr);
+}
+extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+fa2_dv_seg_bf16(const unsigned short* __restrict__ q,
+                const unsigned short* __restrict__ k,
+                const unsigned short* __restrict__ dout,
+                const float* __restrict__ lse,
+                unsigned short* __restrict__ dv_part,
+                const int* __restrict__ bounds,
+                int B, int Hq, int Hkv, int S, float scale, int bshd) {
+  fa2_dv_dk_t<false, true>(q, k, nullptr, dout, lse, nullptr, dv_part, Hq, Hkv, S, scale, bshd,
+                           bounds);
 }
 
 extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
@@ -395,7 +504,19 @@ fa2_dk_bf16(const unsigned short* __restrict__ q,
             const float* __restrict__ delta,
             unsigned short* __restrict__ dk_part,
             int B, int Hq, int Hkv, int S, float scale, int bshd) {
-  fa2_dv_dk_t<true>(q, k, v, dout, lse, delta, dk_part, Hq, Hkv, S, scale, bshd);
+  fa2_dv_dk_t<true, false>(q, k, v, dout, lse, delta, dk_part, Hq, Hkv, S, scale, bshd, nullptr);
+}
+extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+fa2_dk_seg_bf16(const unsigned short* __restrict__ q,
+                const unsigned short* __restrict__ k,
+                const unsigned short* __restrict__ v,
+                const unsigned short* __restrict__ dout,
+                const float* __restrict__ lse,
+                const float* __restrict__ delta,
+                unsigned short* __restrict__ dk_part,
+                const int* __restrict__ bounds,
+                int B, int Hq, int Hkv, int S, float scale, int bshd) {
+  fa2_dv_dk_t<true, true>(q, k, v, dout, lse, delta, dk_part, Hq, Hkv, S, scale, bshd, bounds);
 }
 
 // ---------------------------------------------------------------------------

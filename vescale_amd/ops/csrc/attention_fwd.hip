@@ -33,6 +33,12 @@
 //     logsumexp [B,H,S] fp32 (ln), matching
 //     the stock flash convention so EITHER backward (ours or the
 //     library's) can consume it.
+//   - packed documents (fa_fwd_seg_bf16, template SEG): documents are runs of
+//     equal segment ids; a pre-pass (fa_seg_bounds_i32) writes each position's
+//     run start and end, a lane keeps ONE integer (its row's start), the block
+//     starts at its first row's document (the prologue stages THAT tile) and
+//     a wave computes and masks by two scalars.  fa_fwd_bf16 is the SEG=false
+//     instantiation: the instructions it had before the template.
 // Capability parity: reference vescale relies on library flash attention;
 // this is the MI355X-native forward for the train step's hot op.
 #include "fa32_common.h"
@@ -44,13 +50,16 @@
 #define FF_THREADS (FF_WAVES * 64)
 #define FF_CHUNKS FF_STAGE_CHUNKS(FF_KV, FF_THREADS)  // staging chunks per thread per tile
 
-template <int MODE>  // 0=full, 1=no-softmax, 2=no-PV, 3=no-ST, 4=no-gating, 5=exp-domain (bisect)
+// SEG: the packed-document mask of fa32_common.h (bounds [B,2,S] from the
+// pre-pass; null and never read when !SEG).
+template <int MODE, bool SEG = false>  // 0=full, 1=no-softmax, 2=no-PV, 3=no-ST, 4=no-gating, 5=exp-domain (bisect)
 DEV void fa_fwd_t(const unsigned short* __restrict__ q,
             const unsigned short* __restrict__ k,
             const unsigned short* __restrict__ v,
             unsigned short* __restrict__ out,
             float* __restrict__ lse,
-            int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
+            int B, int Hq, int Hkv, int S, float scale, int out_bshd,
+            const int* __restrict__ bounds = nullptr) {
   __shared__ unsigned short lk[2][FF_KV * FF_D];  // K, swizzled
   __shared__ unsigned short lv[2][FF_KV * FF_D];  // V, swizzled (same as K)
 
@@ -83,21 +92,41 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
   const int n_kv = (qt + 1) * (FF_QTILE / FF_KV);
   const int last_kv = min(n_kv, S / FF_KV);
 
+  // SEG: one integer per lane, the first key of its row's document; the mask
+  // is my_start <= kv <= my_q.  start is monotone, so the wave's first row
+  // (lane 0) holds the wave's minimum, its last row (lane 31) the maximum, and
+  // the block's first row the block's minimum: the block's first kv tile.  It
+  // is block-uniform (all 4 waves stage and reach the same barriers) and held
+  // to [0, last_kv - 1] whatever bounds contains.
+  int my_start = 0, wstart_lo = 0, wstart_hi = 0, first_kv = 0;
+  if constexpr (SEG) {
+    const int* start = ff_seg_start(bounds, c.b, S);
+    my_start = start[my_q];
+    wstart_lo = __builtin_amdgcn_readfirstlane(my_start);
+    wstart_hi = __builtin_amdgcn_readlane(my_start, 31);
+    first_kv = ff_seg_tile(start[qt * FF_QTILE] / FF_KV, 0, last_kv - 1);
+  }
+
+  // the prologue stages the block's first tile (tile 0 without SEG) into the
+  // buffer the loop reads it from (buf = jkv & 1)
   const unsigned short* kg = k + c.kbase;
   const unsigned short* vg = v + c.kbase;
+  const unsigned short* kg0 = kg + (int64_t)first_kv * (FF_KV * FF_D);
+  const unsigned short* vg0 = vg + (int64_t)first_kv * (FF_KV * FF_D);
+  const int buf0 = first_kv & 1;
   // staging registers: tile elems / threads / 8 chunks per thread
   ff_shortx8 kreg[FF_CHUNKS], vreg[FF_CHUNKS];
 #pragma unroll
   for (int j = 0; j < FF_CHUNKS; ++j) {
     const int e = ff_chunk<FF_THREADS>(j, tid);
-    kreg[j] = ff_chunk_load(kg, e);
-    vreg[j] = ff_chunk_load(vg, e);
+    kreg[j] = ff_chunk_load(kg0, e);
+    vreg[j] = ff_chunk_load(vg0, e);
   }
 #pragma unroll
   for (int j = 0; j < FF_CHUNKS; ++j) {
     const int e = ff_chunk<FF_THREADS>(j, tid);
-    ff_chunk_store(kreg[j], lk[0], e);
-    ff_chunk_store(vreg[j], lv[0], e);
+    ff_chunk_store(kreg[j], lk[buf0], e);
+    ff_chunk_store(vreg[j], lv[buf0], e);
   }
   // Retire every vector load here (s_waitcnt vmcnt(0); expcnt and lgkmcnt
   // fields left at "no wait").  The compiler schedules the 8 Q-fragment loads
@@ -113,7 +142,7 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
   __builtin_amdgcn_s_waitcnt(0x0F70);
   __syncthreads();
 
-  for (int jkv = 0; jkv < last_kv; ++jkv) {
+  for (int jkv = first_kv; jkv < last_kv; ++jkv) {
     const int kv0 = jkv * FF_KV;
     const int buf = jkv & 1;
     const bool have_next = (jkv + 1 < last_kv);
@@ -121,9 +150,19 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
     // tile skips ALL compute (it still stages + hits the barrier). Active
     // tiles always satisfy kv0 <= q0 <= min(my_q), so no lane is ever
     // fully masked and no -inf/-inf NaN guards are needed.
-    const bool active = (MODE == 4) || (kv0 <= q0 + FF_QBLK - 1);
+    // SEG: the wave is also inactive while the tile lies before its first
+    // row's document, and also masks while the tile begins before its last
+    // row's document.  A wave that straddles a document boundary then HAS
+    // lanes whose whole tile is masked (their document begins after it): the
+    // dead-lane guard below is theirs.  Tiles inside one document stay on the
+    // unmasked path.
+    bool active = (MODE == 4) || (kv0 <= q0 + FF_QBLK - 1);
     // wave-uniform mask need: only diagonal tiles pay the per-element cmp
-    const bool need_mask = (MODE == 4) || (kv0 + FF_KV - 1 > q0);
+    bool need_mask = (MODE == 4) || (kv0 + FF_KV - 1 > q0);
+    if constexpr (SEG) {
+      active = active && (kv0 + FF_KV - 1 >= wstart_lo);
+      need_mask = need_mask || (kv0 < wstart_hi);
+    }
     // issue next tile's global loads BEFORE compute (latency overlap)
     if (have_next) {
       const unsigned short* kn = kg + (int64_t)(kv0 + FF_KV) * FF_D;
@@ -167,7 +206,8 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           int kv = ff_drow(kv0 + s2 * 32, r, half);
-          float x = (kv <= my_q) ? st[s2][r] * scale2 : -INFINITY;
+          const bool vis = SEG ? (kv <= my_q && kv >= my_start) : (kv <= my_q);
+          float x = vis ? st[s2][r] * scale2 : -INFINITY;
           st[s2][r] = x;
           pmax = fmaxf(pmax, x);
         }
@@ -186,10 +226,23 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
     float m_new = fmaxf(m_run, pmax);  // finite: active tiles have kv0 <= my_q
     bool dead = false;
     if constexpr (MODE == 4) dead = (m_new == -INFINITY);
+    // SEG dead lane: nothing seen yet and nothing in this tile (m_run = m_new =
+    // -inf).  The exponentials below take 0 in place of m_new: corr =
+    // exp2(-inf - 0) = 0 and is then set to 1, p = exp2(-inf - 0) = 0 for all
+    // 32 elements with no select per element, and no exp2(-inf - -inf) is
+    // evaluated.  m_run stays -inf, so the lane comes alive at its document's
+    // first tile exactly like a lane at its first tile.
+    bool seg_dead = false;
+    float m_exp = m_new;
+    if constexpr (SEG) {
+      seg_dead = (m_new == -INFINITY);
+      m_exp = seg_dead ? 0.f : m_new;
+    }
     float corr;
     if constexpr (MODE == 5) corr = __expf(m_run - m_new);
-    else corr = __builtin_amdgcn_exp2f(m_run - m_new);  // m_run=-inf -> 0
+    else corr = __builtin_amdgcn_exp2f(m_run - m_exp);  // m_run=-inf -> 0
     if (dead) { corr = 1.f; m_new = m_run; }
+    if (seg_dead) corr = 1.f;
     float psum = 0.f;
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
@@ -198,7 +251,7 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
         float p;
         if (dead) p = 0.f;
         else if constexpr (MODE == 5) p = (st[s2][r] == -INFINITY) ? 0.f : __expf(st[s2][r] - m_new);
-        else p = __builtin_amdgcn_exp2f(st[s2][r] - m_new);  // -inf -> 0
+        else p = __builtin_amdgcn_exp2f(st[s2][r] - m_exp);  // -inf -> 0
         st[s2][r] = p;
         psum += p;
       }
@@ -293,4 +346,22 @@ fa_fwd_bf16_ab5(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
                 int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
   fa_fwd_t<5>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
+}
+
+// ---- packed documents: the pre-pass and the SEG forward ----
+// ids [B,S] -> bounds [B,2,S] (fa32_common.h); grid (ceil(S/256), B)
+extern "C" __global__ void __launch_bounds__(FF_SEG_THREADS)
+fa_seg_bounds_i32(const int* ids, int* bounds, int S) {
+  ff_seg_bounds(ids, bounds, S);
+}
+// fa_fwd_bf16 with the packed-document mask.  Resources (hipcc -O3
+// --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage): 240 VGPRs, 0
+// AGPRs, 64 KiB LDS, scratch 0, no spills, 2 waves/SIMD (fa_fwd_bf16: 242, the
+// rest equal); the pre-pass 18 VGPRs, 1 KiB LDS, 8 waves/SIMD.
+extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
+fa_fwd_seg_bf16(const unsigned short* q, const unsigned short* k,
+                const unsigned short* v, unsigned short* out, float* lse,
+                const int* bounds, int B, int Hq, int Hkv, int S, float scale,
+                int out_bshd) {
+  fa_fwd_t<0, true>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd, bounds);
 }

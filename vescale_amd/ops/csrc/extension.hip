@@ -639,15 +639,28 @@ FaShape fa_check(const Binding& b, int tile, const at::Tensor& q, const at::Tens
 }
 static_assert(FB_D == FF_D, "tuned attention kernels share D");
 
-// out_bshd: o is allocated and written as [B,S,Hq,D]; lse stays [B,Hq,S]
+// out_bshd: o is allocated and written as [B,S,Hq,D]; lse stays [B,Hq,S].
+// segment_ids [B,S] int32 (packed documents = maximal runs of equal ids): the
+// pre-pass turns them into bounds [B,2,S] (run start, run end), the SEG
+// forward masks with them, and bounds is returned third for fa_bwd2.
 std::vector<at::Tensor> fa_fwd_impl(const Binding& b, int64_t mode, at::Tensor q,
                                     at::Tensor k, at::Tensor v, double scale,
-                                    bool out_bshd) {
+                                    bool out_bshd, const OptTensor& segment_ids = {}) {
   FaShape s = fa_check(b, FF_QTILE, q, k, v);
   TORCH_CHECK(!out_bshd || (int64_t)s.Hq * FF_D <= INT_MAX, b.fn,
               ": Hq * 128 must fit int in the [B,S,Hq,D] layout");
+  b.arg("segment_ids", segment_ids, I32, {s.B, s.S});
   auto out = out_bshd ? at::empty({s.B, s.S, s.Hq, FF_D}, q.options()) : at::empty_like(q);
   auto lse = at::empty({s.B, s.Hq, s.S}, q.options().dtype(F32));
+  if (segment_ids.has_value()) {
+    auto bounds = at::empty({s.B, 2, s.S}, q.options().dtype(I32));
+    b.launch(fa_seg_bounds_i32, dim3((s.S + FF_SEG_THREADS - 1) / FF_SEG_THREADS, s.B),
+             FF_SEG_THREADS, segment_ids->data_ptr<int>(), bounds.data_ptr<int>(), s.S);
+    b.launch(fa_fwd_seg_bf16, dim3(s.S / FF_QTILE, s.Hq, s.B), FF_THREADS, bf16(q), bf16(k),
+             bf16(v), bf16_mut(out), lse.data_ptr<float>(), bounds.data_ptr<int>(), s.B, s.Hq,
+             s.Hkv, s.S, (float)scale, out_bshd ? 1 : 0);
+    return {out, lse, bounds};
+  }
   decltype(&fa_fwd_bf16) kerns[] = {fa_fwd_bf16,     fa_fwd_bf16_ab1, fa_fwd_bf16_ab2,
                                     fa_fwd_bf16_ab3, fa_fwd_bf16_ab4, fa_fwd_bf16_ab5};
   b.launch(kerns[mode], dim3(s.S / FF_QTILE, s.Hq, s.B), FF_THREADS, bf16(q), bf16(k), bf16(v),
@@ -657,8 +670,8 @@ std::vector<at::Tensor> fa_fwd_impl(const Binding& b, int64_t mode, at::Tensor q
 }
 
 std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
-                               bool out_bshd) {
-  return fa_fwd_impl(Binding("fa_fwd", "q", q), 0, q, k, v, scale, out_bshd);
+                               bool out_bshd, OptTensor segment_ids) {
+  return fa_fwd_impl(Binding("fa_fwd", "q", q), 0, q, k, v, scale, out_bshd, segment_ids);
 }
 
 std::vector<at::Tensor> fa_fwd_ablate(at::Tensor q, at::Tensor k, at::Tensor v,
@@ -693,14 +706,21 @@ at::Tensor fa_bwd_reduce(const Binding& b, const FaShape& s, const at::Tensor& p
 // ------------------------------ flash-attention backward v2 ---------------
 std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                 at::Tensor dout, at::Tensor lse, double scale,
-                                bool fused_dvdk, bool bshd) {
+                                bool fused_dvdk, bool bshd, OptTensor seg_bounds) {
   // 32x32-MFMA backward (attention_bwd2.hip): preprocess + dq + dv + dk
   // (+ GQA reduction); lse ln-domain.  bshd: o and dout are [B,S,Hq,D] (the
-  // split kernels only); dq/dk/dv are [B,H,S,D] either way.
+  // split kernels only); dq/dk/dv are [B,H,S,D] either way.  seg_bounds
+  // [B,2,S] int32, the third result of fa_fwd(.., segment_ids=): the SEG dq,
+  // dv and dk kernels (split only).  The kernels hold every tile index they
+  // derive from its content to the range of the unmasked kernels.
   Binding b("fa_bwd2", "q", q);
   TORCH_CHECK(!(bshd && fused_dvdk), "fa_bwd2: the fused dv+dk kernel reads [B,Hq,S,D] ",
               "only: bshd=True needs fused_dvdk=False");
+  TORCH_CHECK(!(seg_bounds.has_value() && fused_dvdk), "fa_bwd2: the fused dv+dk kernel has ",
+              "no segment mask: seg_bounds needs fused_dvdk=False");
   FaShape s = fa_check(b, FB_TILE, q, k, v, o, dout, lse, bshd);
+  b.arg("seg_bounds", seg_bounds, I32, {s.B, 2, s.S});
+  const int* pb = seg_bounds.has_value() ? seg_bounds->data_ptr<int>() : nullptr;
   // the kernels write -inf into the masked scores BEFORE scaling them
   // (ff_mask): only a positive finite scale keeps them -inf
   TORCH_CHECK(scale > 0 && std::isfinite(scale), b.fn, ": scale = ", scale,
@@ -708,9 +728,14 @@ std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Te
   auto delta = fa_bwd_delta(b, s, dout, o, bshd);
   auto dq = at::empty_like(q);
   dim3 grid(s.S / FB_TILE, s.Hq, s.B);
-  b.launch(fa2_dq_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
-           lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), s.B, s.Hq,
-           s.Hkv, s.S, (float)scale, bshd ? 1 : 0);
+  if (pb)
+    b.launch(fa2_dq_seg_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+             lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), pb, s.B, s.Hq,
+             s.Hkv, s.S, (float)scale, bshd ? 1 : 0);
+  else
+    b.launch(fa2_dq_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+             lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), s.B, s.Hq,
+             s.Hkv, s.S, (float)scale, bshd ? 1 : 0);
   auto dv_part = at::empty_like(q);
   auto dk_part = at::empty_like(q);
   if (fused_dvdk) {
@@ -720,6 +745,13 @@ std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Te
              bf16(k), bf16(v), bf16(dout), lse.data_ptr<float>(),
              delta.data_ptr<float>(), bf16_mut(dv_part), bf16_mut(dk_part), s.B, s.Hq,
              s.Hkv, s.S, (float)scale);
+  } else if (pb) {
+    b.launch(fa2_dv_seg_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(dout),
+             lse.data_ptr<float>(), bf16_mut(dv_part), pb, s.B, s.Hq, s.Hkv, s.S,
+             (float)scale, bshd ? 1 : 0);
+    b.launch(fa2_dk_seg_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+             lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dk_part), pb, s.B,
+             s.Hq, s.Hkv, s.S, (float)scale, bshd ? 1 : 0);
   } else {
     b.launch(fa2_dv_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(dout),
              lse.data_ptr<float>(), bf16_mut(dv_part), s.B, s.Hq, s.Hkv, s.S,
@@ -949,9 +981,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_bwd", &fa_bwd);
   m.def("fa_bwd2", &fa_bwd2, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
         pybind11::arg("o"), pybind11::arg("dout"), pybind11::arg("lse"),
-        pybind11::arg("scale"), pybind11::arg("fused_dvdk"), pybind11::arg("bshd") = false);
+        pybind11::arg("scale"), pybind11::arg("fused_dvdk"), pybind11::arg("bshd") = false,
+        pybind11::arg("seg_bounds") = pybind11::none());
   m.def("fa_fwd", &fa_fwd, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
-        pybind11::arg("scale"), pybind11::arg("out_bshd") = false);
+        pybind11::arg("scale"), pybind11::arg("out_bshd") = false,
+        pybind11::arg("segment_ids") = pybind11::none());
   m.def("fa_fwd_ablate", &fa_fwd_ablate);
   m.def("fa_gen_fwd", &fa_gen_fwd, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("causal"),

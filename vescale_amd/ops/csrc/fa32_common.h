@@ -230,6 +230,110 @@ DEV void ff_mask(ff_floatx16 (&st)[2], int lim) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Packed-document ("contiguous segments") mask of the SEG instantiations.
+// The documents of a batch row are the maximal runs of equal segment ids; the
+// pre-pass below turns ids [B,S] into bounds [B,2,S]:
+//   start[b][i] = first position of i's run, end[b][i] = one past its last.
+// Key j is visible to query i iff start[i] <= j <= i, which is the same as
+// j <= i < end[j].  Both rows are monotone non-decreasing in i, so the bound of
+// a block's (or wave's) FIRST row is the minimum over its rows and that of its
+// LAST row the maximum: tile skipping needs one scalar per block and two per
+// wave, and the mask one integer per lane (its own row's start or end).
+// ---------------------------------------------------------------------------
+#define FF_SEG_THREADS 256
+#define FF_SEG_NONE 0x7fffffff  // "no LAST seen yet" of the end scan
+
+DEV const int* ff_seg_start(const int* __restrict__ bounds, int b, int S) {
+  return bounds + (int64_t)b * 2 * S;
+}
+DEV const int* ff_seg_end(const int* __restrict__ bounds, int b, int S) {
+  return bounds + ((int64_t)b * 2 + 1) * S;
+}
+// A tile index derived from the CONTENT of bounds, held to [lo, hi]: whatever
+// the tensor holds, no address is formed from it outside the tiles the kernel
+// without a mask would touch.
+DEV int ff_seg_tile(int t, int lo, int hi) { return max(lo, min(t, hi)); }
+
+// Inclusive block scan over FF_SEG_THREADS values in LDS (Hillis-Steele):
+// MAX ? running maximum towards higher t : running minimum towards lower t.
+template <bool MAX>
+DEV int ff_seg_scan(int* l, int t, int x) {
+  l[t] = x;
+  __syncthreads();
+#pragma unroll
+  for (int off = 1; off < FF_SEG_THREADS; off <<= 1) {
+    const int o = MAX ? t - off : t + off;
+    const bool in = MAX ? o >= 0 : o < FF_SEG_THREADS;
+    const int y = in ? l[o] : x;
+    __syncthreads();
+    x = MAX ? max(x, y) : min(x, y);
+    l[t] = x;
+    __syncthreads();
+  }
+  return x;
+}
+
+// The pre-pass.  grid (ceil(S / 256), B), 256 threads, one position each.
+// A position is a run START when it is 0 or its id differs from the one
+// before, and a run's LAST when it is S - 1 or the id after differs.  start is
+// the running maximum of the START positions, end the running minimum (from
+// the right) of LAST + 1.  A block first scans its own 256 positions; where
+// its chunk holds no START at or before a position (no LAST at or after), the
+// whole block walks the chunks before (after) it, 256 positions at a time,
+// until one holds a flag: position 0 is always a START and S - 1 a LAST, so
+// both walks end.  The walks are block-uniform (every thread reaches every
+// barrier), read-only, and their length is the run's, in chunks.  No atomics:
+// every output word is written once, by its own thread, from values that do
+// not depend on the order blocks run in.
+DEV void ff_seg_bounds(const int* __restrict__ ids, int* __restrict__ bounds, int S) {
+  __shared__ int l[FF_SEG_THREADS];
+  const int t = threadIdx.x, b = blockIdx.y;
+  const int p0 = blockIdx.x * FF_SEG_THREADS;
+  const int* row = ids + (int64_t)b * S;
+  // is position i (0 <= i < S) a START / a LAST?
+  auto is_start = [&](int i) { return i == 0 || row[i] != row[i - 1]; };
+  auto is_last = [&](int i) { return i == S - 1 || row[i] != row[i + 1]; };
+
+  const int i = p0 + t;
+  const bool in = i < S;
+  int st = ff_seg_scan<true>(l, t, (in && is_start(i)) ? i : -1);
+  // l[0] after the scan is thread 0's own value: -1 iff p0 is no START, and
+  // then every position up to the chunk's first START needs the walk
+  int carry = -1;
+  if (l[0] < 0) {
+    // p0 > 0 here (position 0 is a START), so c >= 0 throughout
+    for (int c = p0 - FF_SEG_THREADS; carry < 0; c -= FF_SEG_THREADS) {
+      __syncthreads();
+      ff_seg_scan<true>(l, t, is_start(c + t) ? c + t : -1);
+      carry = l[FF_SEG_THREADS - 1];  // the chunk's last START, -1 if none
+    }
+  }
+  st = max(st, carry);
+  __syncthreads();
+
+  int en = ff_seg_scan<false>(l, t, (in && is_last(i)) ? i + 1 : FF_SEG_NONE);
+  // the chunk's last valid position holds FF_SEG_NONE iff it is no LAST, and then
+  // it (and what precedes it back to the chunk's last LAST) needs the walk
+  const int tail = min(FF_SEG_THREADS, S - p0) - 1;
+  int ecarry = FF_SEG_NONE;
+  if (l[tail] == FF_SEG_NONE) {
+    // the tail is no LAST, so it is not S - 1 and the next chunk exists
+    for (int c = p0 + FF_SEG_THREADS; ecarry == FF_SEG_NONE; c += FF_SEG_THREADS) {
+      __syncthreads();
+      const int j = c + t;
+      ff_seg_scan<false>(l, t, (j < S && is_last(j)) ? j + 1 : FF_SEG_NONE);
+      ecarry = l[0];  // the chunk's first LAST + 1, FF_SEG_NONE if none
+    }
+  }
+  en = min(en, ecarry);
+  if (in) {
+    int* out = bounds + (int64_t)b * 2 * S;
+    out[i] = st;
+    out[S + i] = en;
+  }
+}
+
 // 8 tr reads (4 ks x 2) of a TRANSPOSED A-operand from a swizzled 64x128
 // tile: fragment[lane-dim = ds*32 + l31][k = ks*16 + half*8 + e] is
 // ff_cat(t[ks][0], t[ks][1]).  Probe-measured ds_read_b64_tr_b16 semantics

@@ -523,7 +523,8 @@ def vocab_parallel_cross_entropy(
 # ---------------------------------------------------------------------------
 # Tuned flash attention: our CDNA4 MFMA forward (ops/csrc/attention_fwd.hip,
 # returns logsumexp) + backward (ops/csrc/attention_bwd2.hip); causal,
-# head_dim 128, GQA, seq % 256 == 0.
+# head_dim 128, GQA, seq % 256 == 0; optionally the packed-document mask of
+# flash_attention(..., contiguous_segments=True).
 # ---------------------------------------------------------------------------
 class _FlashAttention(torch.autograd.Function):
     """Causal flash attention, fully on our MFMA kernels: fa_fwd
@@ -542,18 +543,35 @@ class _FlashAttention(torch.autograd.Function):
     (profiles/streaming_kernels_r3.txt)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale):
+    def forward(ctx, q, k, v, scale, seg_ids=None):
         # q,k,v: [B, H, S, D] contiguous bf16.  The kernel writes o as
         # [B, S, H, D], the layout the output projection reads; callers get
         # the [B, H, S, D]-shaped view of it.
-        out, lse = _ext().fa_fwd(q, k, v, scale, out_bshd=True)
+        # seg_ids [B, S] int32 contiguous: packed documents as runs of equal
+        # ids.  fa_fwd derives the run bounds [B, 2, S] once and hands them
+        # back; they are saved for fa_bwd2's SEG kernels.
+        if seg_ids is None:
+            out, lse = _ext().fa_fwd(q, k, v, scale, out_bshd=True)
+            bounds = None
+        else:
+            out, lse, bounds = _ext().fa_fwd(q, k, v, scale, out_bshd=True,
+                                             segment_ids=seg_ids)
         ctx.save_for_backward(q, k, v, out, lse)
+        ctx.bounds = bounds
         ctx.scale = scale
         return out.transpose(1, 2)
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
+        if ctx.bounds is not None:
+            # the fused dv+dk kernel has no segment mask: always the split ones
+            dout = dout.transpose(1, 2)
+            if not dout.is_contiguous():
+                dout = dout.contiguous()
+            dq, dk, dv = _ext().fa_bwd2(q, k, v, out, dout, lse, ctx.scale, False,
+                                        bshd=True, seg_bounds=ctx.bounds)
+            return dq, dk, dv, None, None
         # default OFF: the fused dv+dk kernel is numerically exact but
         # measured SLOWER (whole bwd 17.9 ms vs 11.2 ms at B4 H32/8 S8192,
         # profiles/fa_fused_dvdk_ab_r2.log) — its 2-accumulator register set
@@ -565,14 +583,14 @@ class _FlashAttention(torch.autograd.Function):
             dq, dk, dv = _ext().fa_bwd2(
                 q, k, v, out.transpose(1, 2).contiguous(), dout.contiguous(), lse,
                 ctx.scale, True)
-            return dq, dk, dv, None
+            return dq, dk, dv, None, None
         # the gradient of the [B, H, S, D] view of a [B, S, H*D] consumer is
         # contiguous once transposed back: no copy on the model's path
         dout = dout.transpose(1, 2)
         if not dout.is_contiguous():
             dout = dout.contiguous()
         dq, dk, dv = _ext().fa_bwd2(q, k, v, out, dout, lse, ctx.scale, False, bshd=True)
-        return dq, dk, dv, None
+        return dq, dk, dv, None, None
 
 
 def flash_attention_causal(q, k, v):
@@ -712,8 +730,21 @@ def segment_ids_from_cu_seqlens(cu_seqlens, total: int) -> torch.Tensor:
     return ids.to(torch.int32)
 
 
+def _run_start_ids(ids):
+    """ids [B, S] -> int32 [B, S], every position's id replaced by the first
+    position of its maximal run of equal ids: equal run start <=> same run, so
+    the equality mask over the result is the run mask.  A boundary flag and a
+    running maximum on the ids' device; no host sync."""
+    S = ids.shape[1]
+    pos = torch.arange(S, device=ids.device, dtype=torch.int32).expand_as(ids)
+    edge = torch.ones_like(ids, dtype=torch.bool)
+    edge[:, 1:] = ids[:, 1:] != ids[:, :-1]
+    return torch.cummax(torch.where(edge, pos, torch.zeros_like(pos)), dim=1).values
+
+
 def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
-                    return_lse=False, q_segment_ids=None, kv_segment_ids=None):
+                    return_lse=False, q_segment_ids=None, kv_segment_ids=None,
+                    contiguous_segments=False):
     """Attention over q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (Hq % Hkv == 0).
 
     With is_causal, key j is visible to query i iff j <= i + causal_shift
@@ -731,8 +762,22 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
     key carries is a dead row as above; a key no query sees gets zero dk/dv.
     segment_ids_from_cu_seqlens builds ids from document boundaries.
 
+    contiguous_segments=True is the promise that documents are contiguous:
+    the mask is then defined by the MAXIMAL RUNS of equal ids along the
+    sequence, per batch row: key j is visible to query i iff both lie in the
+    same run and j <= i.  For ids from segment_ids_from_cu_seqlens that is
+    the equality mask above.  An id that reappears after its run ended starts
+    a new document (defined behaviour, not an error).  It needs q_segment_ids,
+    is_causal=True, causal_shift == 0, Sq == Sk and no kv_segment_ids
+    (ValueError otherwise).  Every path gives this answer: the tuned D=128
+    kernels mask by run bounds; everywhere else the ids are replaced on the
+    device by their run's first position and go to the general kernel or the
+    reference unchanged.  VESCALE_FA_SEG=gen keeps such calls off the tuned
+    kernels (A/B).
+
     Dispatch: (1) the tuned D=128 causal kernels when their gate holds, no
-    lse is wanted and there are no segment ids; (2) the general HIP kernel
+    lse is wanted and there are no segment ids, or the ids come with
+    contiguous_segments; (2) the general HIP kernel
     for bf16 on GPU with D in {64, 128}; (3) the torch reference (CPU, other
     dtypes / head dims, VESCALE_FA=aten)."""
     import math
@@ -741,6 +786,16 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
         raise ValueError("causal_shift != 0 requires is_causal=True")
     B, Hq, Sq, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
+    if contiguous_segments:
+        if q_segment_ids is None:
+            raise ValueError("contiguous_segments=True requires q_segment_ids")
+        if kv_segment_ids is not None:
+            raise ValueError("contiguous_segments=True takes no kv_segment_ids: "
+                             "the documents of q and k/v are the same runs")
+        if not is_causal or causal_shift != 0 or Sq != Sk:
+            raise ValueError("contiguous_segments=True requires is_causal=True, "
+                             f"causal_shift == 0 and Sq == Sk (got is_causal={is_causal}, "
+                             f"causal_shift={causal_shift}, Sq={Sq}, Sk={Sk})")
     q_seg, kv_seg = _segment_args(q_segment_ids, kv_segment_ids, B, Sq, Sk)
     if scale is None:
         scale = 1.0 / math.sqrt(D)
@@ -752,10 +807,14 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
         and _use_hip(q, k, v)
     )
     if (hip and not return_lse and is_causal and causal_shift == 0
-            and Sq == Sk and D == 128 and Sq % 256 == 0 and q_seg is None):
+            and Sq == Sk and D == 128 and Sq % 256 == 0
+            and (q_seg is None or (contiguous_segments and
+                                   os.environ.get("VESCALE_FA_SEG", "tuned") != "gen"))):
         return _FlashAttention.apply(
-            q.contiguous(), k.contiguous(), v.contiguous(), scale
+            q.contiguous(), k.contiguous(), v.contiguous(), scale, q_seg
         )
+    if contiguous_segments:
+        q_seg = kv_seg = _run_start_ids(q_seg)
     if hip:
         out, lse = _FlashAttentionGen.apply(
             q.contiguous(), k.contiguous(), v.contiguous(), float(scale),
