@@ -2,7 +2,7 @@
 //
 // The tuned backward: the patterns proven out in attention_fwd.hip, through
 // the same fa32_common.h helpers
-// (ff_stage swizzled staging, ff_relayout permlane relayout, ff_tr_read8
+// (ff_stage_async direct, double-buffered swizzled staging, ff_relayout permlane relayout, ff_tr_read8
 // 4x4-group ds_read_b64_tr_b16 transpose reads — all probe-verified on
 // hardware, tools/tr_probe_check.py).  ff_tr_read8 reads only the low 4 bits
 // of its l15 argument; these kernels hand it tid.
@@ -139,9 +139,11 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
             unsigned short* __restrict__ dq,
             int B, int Hq, int Hkv, int S, float scale, int bshd,
             const int* __restrict__ bounds) {
-  __shared__ unsigned short lk[FB_OTH * FB_D];    // K kv-tile (swz)
-  __shared__ unsigned short lv[FB_OTH * FB_D];    // V kv-tile (swz)
-  __shared__ unsigned short ldo[FB_TILE * FB_D];  // block's dO q rows (swz)
+  // 2 x 16 + 2 x 16 + 64 = 128 KiB of the CU's 160: one block per CU, as the
+  // 256 VGPRs of its 8 waves decide anyway
+  __shared__ unsigned short lk[2][FB_OTH * FB_D];  // K kv-tile (swz), double-buffered
+  __shared__ unsigned short lv[2][FB_OTH * FB_D];  // V kv-tile (swz), double-buffered
+  __shared__ unsigned short ldo[FB_TILE * FB_D];   // block's dO q rows (swz)
 
   const ff_ctx c = ff_prologue(Hq, Hkv, S);
   const int tid = c.tid, l31 = c.l31, half = c.half;
@@ -168,10 +170,11 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
   // Q fragments (B-operand, like the fwd's qf)
   ff_shortx8 qf[8];
   ff_row_frags(q + qbase + (int64_t)my_q * FB_D, qf, half);
-  // stage the block's FB_TILE dO rows once (swizzled)
+  // stage the block's FB_TILE dO rows once (swizzled), by direct global -> LDS
+  // loads: they land under the first tile's wait + barrier
   // (dout is [B,Hq,S,D] or, bshd, [B,S,Hq,D]: a row stride and a head base)
   const ff_rows dorow = ff_o_rows(c, Hq, S, bshd);
-  ff_stage_rows<FB_TILE, FB_THREADS>(
+  ff_stage_async<FB_TILE, FB_THREADS>(
       dout + dorow.base + (int64_t)qt * FB_TILE * dorow.stride, dorow.stride, ldo, tid);
 
   ff_floatx16 dqacc[4];
@@ -195,8 +198,19 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
     first_kv = ff_seg_tile(start[qt * FB_TILE] / FB_OTH, 0, last_kv);
   }
 
+  // K/V tiles double-buffered by direct loads (ff_stage_async), buffer = tile
+  // index & 1 (with SEG the first tile need not be even).  The guard is
+  // block-uniform: with first_kv == last_kv there is no tile and no address.
+  if (first_kv < last_kv) {
+    ff_stage_async<FB_OTH, FB_THREADS>(kg + (int64_t)first_kv * (FB_OTH * FB_D), FB_D,
+                                       lk[first_kv & 1], tid);
+    ff_stage_async<FB_OTH, FB_THREADS>(vg + (int64_t)first_kv * (FB_OTH * FB_D), FB_D,
+                                       lv[first_kv & 1], tid);
+  }
+
   for (int jkv = first_kv; jkv < last_kv; ++jkv) {
     const int kv0 = jkv * FB_OTH;
+    const int buf = jkv & 1;
     bool active = (kv0 <= q0 + FB_OWN - 1);
     const bool need_mask = (kv0 + FB_OTH - 1 > q0);
     // SEG: inactive while the tile lies before the wave's first document; the
@@ -206,10 +220,18 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
       active = active && (kv0 + FB_OTH - 1 >= wstart_lo);
       need_seg = kv0 < wstart_hi;
     }
-    __syncthreads();  // previous tile's readers done
-    ff_stage<FB_OTH, FB_THREADS>(kg + (int64_t)kv0 * FB_D, lk, tid);
-    ff_stage<FB_OTH, FB_THREADS>(vg + (int64_t)kv0 * FB_D, lv, tid);
+    // One wait and one barrier per tile: this wave's loads of tile jkv (and
+    // of dO, the first time) have landed; after the barrier the tile is
+    // visible to all waves and all of them are done reading tile jkv - 1, whose
+    // buffer the loads of tile jkv + 1 then fill while this one is computed.
+    // Every wave issues them, active or not; the guard is block-uniform and
+    // the last iteration forms no address.
+    ff_stage_wait();
     __syncthreads();
+    if (jkv + 1 < last_kv) {
+      ff_stage_async<FB_OTH, FB_THREADS>(kg + (int64_t)(kv0 + FB_OTH) * FB_D, FB_D, lk[buf ^ 1], tid);
+      ff_stage_async<FB_OTH, FB_THREADS>(vg + (int64_t)(kv0 + FB_OTH) * FB_D, FB_D, lv[buf ^ 1], tid);
+    }
 
     if (active) {
       // ST' = K.Q^T and dP' = V.dO^T — both D[kv][q], col = q = l31
@@ -223,9 +245,9 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-          ff_shortx8 kfr = ff_afrag(lk, s2, ks, l31, half);
+          ff_shortx8 kfr = ff_afrag(lk[buf], s2, ks, l31, half);
           st[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr, qf[ks], st[s2], 0, 0, 0);
-          ff_shortx8 vfr = ff_afrag(lv, s2, ks, l31, half);
+          ff_shortx8 vfr = ff_afrag(lv[buf], s2, ks, l31, half);
           ff_shortx8 dof = ff_bfrag(ldo, wave * FB_OWN + l31, ks, half);
           dp[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr, dof, dp[s2], 0, 0, 0);
         }
@@ -249,7 +271,7 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
 #pragma unroll
       for (int ds = 0; ds < 4; ++ds) {
         ff_shortx4 t[4][2];
-        ff_tr_read8(lk, ds, tid, l31, half, t);
+        ff_tr_read8(lk[buf], ds, tid, l31, half, t);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
           dqacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
@@ -257,6 +279,10 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
       }
     }
   }
+
+  // (no tile at all: the dO loads are still in flight; nothing may be pending
+  // when the wave ends)
+  ff_stage_wait();
 
   // epilogue: dQ[q][d] = scale * acc (D-layout: rows = d, col = q = l31).
   // The row address and `half` are worked out again here, from the scalar
@@ -273,7 +299,7 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
   ff_store_row(dq + qbase + (int64_t)e_q * FB_D, dqacc, scale, elane >> 5);
 }
 
-extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
 fa2_dq_bf16(const unsigned short* __restrict__ q,
             const unsigned short* __restrict__ k,
             const unsigned short* __restrict__ v,
@@ -284,14 +310,13 @@ fa2_dq_bf16(const unsigned short* __restrict__ q,
             int B, int Hq, int Hkv, int S, float scale, int bshd) {
   fa2_dq_t<false>(q, k, v, dout, lse, delta, dq, B, Hq, Hkv, S, scale, bshd, nullptr);
 }
-// Resources of the SEG instantiations (hipcc -O3 --offload-arch=gfx950,
-// -Rpass-analysis=kernel-resource-usage), each equal to its SEG=false sibling
-// and at 2 waves/SIMD with scratch 0 and no spills:
-//   fa2_dq_seg_bf16  256 VGPRs, 0 AGPRs, 96 KiB LDS    (my_start is live across
-//                    the loop; the mask's second bound costs SGPRs, 83 -> 87)
-//   fa2_dv_seg_bf16  188 VGPRs, 0 AGPRs, 33024 B LDS
-//   fa2_dk_seg_bf16  254 VGPRs, 0 AGPRs, 33280 B LDS
-extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+// Resources of the SEG instantiations (the extension's flags,
+// -Rpass-analysis=kernel-resource-usage), each within 2 VGPRs of its SEG=false
+// sibling and at 2 waves/SIMD with scratch 0 and no spills:
+//   fa2_dq_seg_bf16  238 VGPRs, 0 AGPRs, 128 KiB LDS
+//   fa2_dv_seg_bf16  188 VGPRs, 0 AGPRs, 66048 B LDS
+//   fa2_dk_seg_bf16  255 VGPRs, 0 AGPRs, 66560 B LDS
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
 fa2_dq_seg_bf16(const unsigned short* __restrict__ q,
                 const unsigned short* __restrict__ k,
                 const unsigned short* __restrict__ v,
@@ -324,10 +349,11 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
                      unsigned short* __restrict__ out_part,
                      int Hq, int Hkv, int S, float scale, int bshd,
                      const int* __restrict__ bounds) {
-  __shared__ unsigned short lq[FB_OTH * FB_D];    // Q q-tile (swz)
-  __shared__ unsigned short ldo[FB_OTH * FB_D];   // dO q-tile (swz)
-  __shared__ float llse[FB_OTH];                  // q-tile rows' lse2
-  __shared__ float ldelta[FB_OTH];                // dk only: never referenced, so never allocated, in dv
+  // every q-tile array double-buffered (buffer = tile index & 1): about 66 KiB
+  __shared__ unsigned short lq[2][FB_OTH * FB_D];   // Q q-tile (swz)
+  __shared__ unsigned short ldo[2][FB_OTH * FB_D];  // dO q-tile (swz)
+  __shared__ float llse[2][FB_OTH];                 // q-tile rows' lse2
+  __shared__ float ldelta[2][FB_OTH];               // dk only: never referenced, so never allocated, in dv
 
   const ff_ctx c = ff_prologue(Hq, Hkv, S);
   const int tid = c.tid, wave = c.wave, l31 = c.l31, half = c.half;
@@ -374,8 +400,27 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
   const float* dltg = DK ? delta + c.rbase : nullptr;
   const ff_rows dorow = ff_o_rows(c, Hq, S, bshd);  // dout in either layout
 
+  // Q and dO tiles double-buffered by direct loads (ff_stage_async).  The lse2
+  // (dk: and delta) row of a tile is 64 floats: the block's first 64 threads
+  // load it beside the direct loads and carry it in a register across the
+  // tile's compute to the other buffer.  The prologue does both for the first
+  // tile; jq0 < S/64, and with SEG the guard is block-uniform.
+  const unsigned short* qg = q + qbase;
+  const unsigned short* dog = dout + dorow.base;
+  if (jq0 < n_jq) {
+    ff_stage_async<FB_OTH, FB_THREADS>(qg + (int64_t)jq0 * (FB_OTH * FB_D), FB_D, lq[jq0 & 1], tid);
+    ff_stage_async<FB_OTH, FB_THREADS>(dog + (int64_t)jq0 * FB_OTH * dorow.stride, dorow.stride,
+                                       ldo[jq0 & 1], tid);
+    if (tid < FB_OTH) {
+      llse[jq0 & 1][tid] = lseg[jq0 * FB_OTH + tid] * FF_LOG2E;
+      if constexpr (DK) ldelta[jq0 & 1][tid] = dltg[jq0 * FB_OTH + tid];
+    }
+  }
+
   for (int jq = jq0; jq < n_jq; ++jq) {
     const int qt0 = jq * FB_OTH;
+    const int buf = jq & 1;
+    const bool have_next = (jq + 1 < n_jq);  // block-uniform
     bool active = (qt0 + FB_OTH - 1 >= kv0w);
     const bool need_mask = (qt0 < kv0w + FB_OWN - 1);
     // SEG: inactive once the tile lies past the wave's last document; the
@@ -385,15 +430,24 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
       active = active && (qt0 < wend_hi);
       need_seg = qt0 + FB_OTH - 1 >= wend_lo;
     }
+    // One wait and one barrier per tile: this wave's loads of tile jq have
+    // landed; after the barrier the tile (and its lse2 / delta row, stored
+    // before it) is visible to all waves and all of them are done reading tile
+    // jq - 1, whose buffers tile jq + 1 then fills while this one is computed.
+    // Every wave issues its loads, active or not; the last iteration forms no
+    // address.
+    ff_stage_wait();
     __syncthreads();
-    ff_stage<FB_OTH, FB_THREADS>(q + qbase + (int64_t)qt0 * FB_D, lq, tid);
-    ff_stage_rows<FB_OTH, FB_THREADS>(dout + dorow.base + (int64_t)qt0 * dorow.stride,
-                                      dorow.stride, ldo, tid);
-    if (tid < FB_OTH) {
-      llse[tid] = lseg[qt0 + tid] * FF_LOG2E;
-      if constexpr (DK) ldelta[tid] = dltg[qt0 + tid];
+    float lse_n = 0.f, dlt_n = 0.f;
+    if (have_next) {
+      ff_stage_async<FB_OTH, FB_THREADS>(qg + (int64_t)(qt0 + FB_OTH) * FB_D, FB_D, lq[buf ^ 1], tid);
+      ff_stage_async<FB_OTH, FB_THREADS>(dog + (int64_t)(qt0 + FB_OTH) * dorow.stride,
+                                         dorow.stride, ldo[buf ^ 1], tid);
+      if (tid < FB_OTH) {
+        lse_n = lseg[qt0 + FB_OTH + tid];
+        if constexpr (DK) dlt_n = dltg[qt0 + FB_OTH + tid];
+      }
     }
-    __syncthreads();
 
     if (active) {
       // ST = Q.K^T (dk: and dP = dO.V^T) -> D[q][kv], col = kv = l31
@@ -414,7 +468,7 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
         // has no room for it.
         ff_shortx8 qfr[16];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) qfr[i] = ff_afrag(lq, i & 1, i >> 1, l31, half);
+        for (int i = 0; i < 16; ++i) qfr[i] = ff_afrag(lq[buf], i & 1, i >> 1, l31, half);
 #pragma unroll
         for (int i = 0; i < 16; ++i)
           st[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr[i], kf[i >> 1], st[i & 1], 0, 0, 0);
@@ -430,9 +484,9 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
         for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
           for (int ks = 0; ks < 8; ++ks) {
-            ff_shortx8 qfr = ff_afrag(lq, s2, ks, l31, half);
+            ff_shortx8 qfr = ff_afrag(lq[buf], s2, ks, l31, half);
             st[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr, kf[ks], st[s2], 0, 0, 0);
-            ff_shortx8 dofr = ff_afrag(ldo, s2, ks, l31, half);
+            ff_shortx8 dofr = ff_afrag(ldo[buf], s2, ks, l31, half);
             dp[s2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dofr, vf[ks], dp[s2], 0, 0, 0);
           }
       }
@@ -448,8 +502,8 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           int qrow = ff_drow(s2 * 32, r, half);
-          float p = __builtin_amdgcn_exp2f(st[s2][r] * scale2 - llse[qrow]);
-          if constexpr (DK) st[s2][r] = p * (dp[s2][r] - ldelta[qrow]);
+          float p = __builtin_amdgcn_exp2f(st[s2][r] * scale2 - llse[buf][qrow]);
+          if constexpr (DK) st[s2][r] = p * (dp[s2][r] - ldelta[buf][qrow]);
           else st[s2][r] = p;
         }
       ff_shortx8 pb[4];
@@ -459,21 +513,27 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
 #pragma unroll
       for (int ds = 0; ds < 4; ++ds) {
         ff_shortx4 t[4][2];
-        ff_tr_read8(DK ? lq : ldo, ds, tid, l31, half, t);
+        ff_tr_read8(DK ? lq[buf] : ldo[buf], ds, tid, l31, half, t);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
           acc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               ff_cat(t[ks][0], t[ks][1]), pb[ks], acc[ds], 0, 0, 0);
       }
     }
+    // the next tile's lse2 / delta row, into the buffer the next barrier opens
+    if (have_next && tid < FB_OTH) {
+      llse[buf ^ 1][tid] = lse_n * FF_LOG2E;
+      if constexpr (DK) ldelta[buf ^ 1][tid] = dlt_n;
+    }
   }
+  ff_stage_wait();  // no tile at all: nothing may be pending when the wave ends
 
   // epilogue (rows = d over regs, col = kv = l31 -> row write); dK = scale * acc
   unsigned short* og = out_part + qbase + (int64_t)my_kv * FB_D;
   ff_store_row<DK>(og, acc, scale, half);
 }
 
-extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
 fa2_dv_bf16(const unsigned short* __restrict__ q,
             const unsigned short* __restrict__ k,
             const unsigned short* __restrict__ dout,
@@ -483,7 +543,7 @@ fa2_dv_bf16(const unsigned short* __restrict__ q,
   fa2_dv_dk_t<false, false>(q, k, nullptr, dout, lse, nullptr, dv_part, Hq, Hkv, S, scale, bshd,
                             nullptr);
 }
-extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
 fa2_dv_seg_bf16(const unsigned short* __restrict__ q,
                 const unsigned short* __restrict__ k,
                 const unsigned short* __restrict__ dout,
@@ -495,7 +555,7 @@ fa2_dv_seg_bf16(const unsigned short* __restrict__ q,
                            bounds);
 }
 
-extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
 fa2_dk_bf16(const unsigned short* __restrict__ q,
             const unsigned short* __restrict__ k,
             const unsigned short* __restrict__ v,
@@ -506,7 +566,7 @@ fa2_dk_bf16(const unsigned short* __restrict__ q,
             int B, int Hq, int Hkv, int S, float scale, int bshd) {
   fa2_dv_dk_t<true, false>(q, k, v, dout, lse, delta, dk_part, Hq, Hkv, S, scale, bshd, nullptr);
 }
-extern "C" __global__ void __launch_bounds__(FB_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
 fa2_dk_seg_bf16(const unsigned short* __restrict__ q,
                 const unsigned short* __restrict__ k,
                 const unsigned short* __restrict__ v,

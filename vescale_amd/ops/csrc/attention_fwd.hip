@@ -13,7 +13,7 @@
 //   - P -> PV B-operand relayout in-register: v_cvt_pk_bf16_f32 pairs +
 //     permlane32_swap (guide T12: one swap fills both half-kv words; no
 //     LDS round trip, no divergent branch)
-//   - V staged EXACTLY like K (row-major + XOR swizzle, vector stores)
+//   - V staged EXACTLY like K (row-major + XOR swizzle, direct loads)
 //     and the PV A-operand (V^T) read with ds_read_b64_tr_b16 (guide
 //     T10): probe-measured semantics (tools/tr_probe_check.py) are a 4x4
 //     transpose within each aligned 4-lane group — lane l elem j receives
@@ -23,9 +23,10 @@
 //     (fa32_lds_map.h) sends the 4 rows to 4 different 64-byte column
 //     bands, so these reads and the K row-fragment reads are both
 //     bank-conflict-free
-//   - K/V tiles DOUBLE-BUFFERED in LDS: tile j+1's global loads issue
-//     before tile j's compute, stores land in the other buffer, ONE
-//     barrier per tile (guide T3/T4 phase overlap, structured form)
+//   - K/V tiles DOUBLE-BUFFERED in LDS by direct global -> LDS loads
+//     (ff_stage_async: no staging register, no ds_write): tile j+1's loads
+//     issue before tile j's compute into the other buffer, ONE wait + ONE
+//     barrier per tile, at its top
 //   - O accumulates in D-layout (col = q), so the online rescale by
 //     exp(m_old - m_new) is a lane-local scalar multiply
 //   - outputs: O [B,H,S,D] (or, out_bshd, [B,S,H,D] — the layout the
@@ -48,7 +49,6 @@
 #define FF_QTILE (FF_QBLK * FF_WAVES)  // 128 q rows per block
 #define FF_KV 64               // kv tile
 #define FF_THREADS (FF_WAVES * 64)
-#define FF_CHUNKS FF_STAGE_CHUNKS(FF_KV, FF_THREADS)  // staging chunks per thread per tile
 
 // SEG: the packed-document mask of fa32_common.h (bounds [B,2,S] from the
 // pre-pass; null and never read when !SEG).
@@ -114,33 +114,13 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
   const unsigned short* kg0 = kg + (int64_t)first_kv * (FF_KV * FF_D);
   const unsigned short* vg0 = vg + (int64_t)first_kv * (FF_KV * FF_D);
   const int buf0 = first_kv & 1;
-  // staging registers: tile elems / threads / 8 chunks per thread
-  ff_shortx8 kreg[FF_CHUNKS], vreg[FF_CHUNKS];
-#pragma unroll
-  for (int j = 0; j < FF_CHUNKS; ++j) {
-    const int e = ff_chunk<FF_THREADS>(j, tid);
-    kreg[j] = ff_chunk_load(kg0, e);
-    vreg[j] = ff_chunk_load(vg0, e);
-  }
-#pragma unroll
-  for (int j = 0; j < FF_CHUNKS; ++j) {
-    const int e = ff_chunk<FF_THREADS>(j, tid);
-    ff_chunk_store(kreg[j], lk[buf0], e);
-    ff_chunk_store(vreg[j], lv[buf0], e);
-  }
-  // Retire every vector load here (s_waitcnt vmcnt(0); expcnt and lgkmcnt
-  // fields left at "no wait").  The compiler schedules the 8 Q-fragment loads
-  // after the tile-0 K/V loads and waits only for the latter before this
-  // barrier, so its scoreboard enters the loop with 8 loads pending and it
-  // puts vmcnt(7)..vmcnt(0) in front of the QK^T MFMAs that read qf[0..7] in
-  // EVERY iteration.  From the second tile on those counts no longer cover Q
-  // but the 8 K/V prefetch loads issued just above them, and the wave stalls
-  // on the prefetch that the double buffer exists to carry across softmax and
-  // PV.  With the scoreboard clean the loop's only vmcnt wait is in front of
-  // the staging stores after PV.  (A builtin, not inline asm: the wait-count
-  // pass does not look inside an asm statement.)
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __syncthreads();
+  // direct global -> LDS loads (ff_stage_async): no staging register, no
+  // ds_write; the loop's first wait + barrier makes the tile readable.
+  // Unguarded, unlike the backward kernels' prologues: last_kv >= 1 (S >= 64,
+  // qt >= 0) and first_kv <= last_kv - 1 (ff_seg_tile above), so the tile
+  // exists and the loop runs at least once.
+  ff_stage_async<FF_KV, FF_THREADS>(kg0, FF_D, lk[buf0], tid);
+  ff_stage_async<FF_KV, FF_THREADS>(vg0, FF_D, lv[buf0], tid);
 
   for (int jkv = first_kv; jkv < last_kv; ++jkv) {
     const int kv0 = jkv * FF_KV;
@@ -163,16 +143,20 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
       active = active && (kv0 + FF_KV - 1 >= wstart_lo);
       need_mask = need_mask || (kv0 < wstart_hi);
     }
-    // issue next tile's global loads BEFORE compute (latency overlap)
+    // One barrier per tile.  ff_stage_wait: this wave's loads of tile jkv (and,
+    // in the first iteration, its Q fragments) have landed; it also leaves the
+    // compiler's scoreboard clean, so no counted vmcnt wait of the prologue's
+    // loads is carried into the QK^T block of every iteration
+    // (NOTES_FA32_LOOPS.md, C).  After the barrier tile jkv is visible to all
+    // waves and every wave is done reading tile jkv - 1, whose buffer the loads
+    // of tile jkv + 1 then fill while this tile is computed.  Every wave issues
+    // them, active or not; have_next is block-uniform and the last iteration
+    // forms no address.
+    ff_stage_wait();
+    __syncthreads();
     if (have_next) {
-      const unsigned short* kn = kg + (int64_t)(kv0 + FF_KV) * FF_D;
-      const unsigned short* vn = vg + (int64_t)(kv0 + FF_KV) * FF_D;
-#pragma unroll
-      for (int j = 0; j < FF_CHUNKS; ++j) {
-        const int e = ff_chunk<FF_THREADS>(j, tid);
-        kreg[j] = ff_chunk_load(kn, e);
-        vreg[j] = ff_chunk_load(vn, e);
-      }
+      ff_stage_async<FF_KV, FF_THREADS>(kg + (int64_t)(kv0 + FF_KV) * FF_D, FF_D, lk[buf ^ 1], tid);
+      ff_stage_async<FF_KV, FF_THREADS>(vg + (int64_t)(kv0 + FF_KV) * FF_D, FF_D, lv[buf ^ 1], tid);
     }
 
     if (active) {
@@ -287,18 +271,11 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
     }
     }  // end relayout+PV (MODE != 2)
     }  // end if (active)
-
-    // store next tile into the other buffer, then one barrier
-    if (have_next) {
-#pragma unroll
-      for (int j = 0; j < FF_CHUNKS; ++j) {
-        const int e = ff_chunk<FF_THREADS>(j, tid);
-        ff_chunk_store(kreg[j], lk[buf ^ 1], e);
-        ff_chunk_store(vreg[j], lv[buf ^ 1], e);
-      }
-    }
-    __syncthreads();
   }
+
+  // the rule of all four kernels: nothing pending when the wave ends (here the
+  // loop's last wait already saw to it)
+  ff_stage_wait();
 
   // ---- epilogue: O[q][d] = acc / l ; lse = m2*ln2 + ln(l) (m2 log2-dom) ----
   float inv_l = (l_run > 0.f) ? 1.0f / l_run : 0.f;
@@ -311,37 +288,37 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
 }
 
 // instantiations: the real kernel + ablation variants for profiling
-extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16(const unsigned short* q, const unsigned short* k,
             const unsigned short* v, unsigned short* out, float* lse,
             int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
   fa_fwd_t<0>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
-extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab1(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
                 int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
   fa_fwd_t<1>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
-extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab2(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
                 int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
   fa_fwd_t<2>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
-extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab3(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
                 int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
   fa_fwd_t<3>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
-extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab4(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
                 int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
   fa_fwd_t<4>(q, k, v, out, lse, B, Hq, Hkv, S, scale, out_bshd);
 }
-extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FF_THREADS, 2)
 fa_fwd_bf16_ab5(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
                 int B, int Hq, int Hkv, int S, float scale, int out_bshd) {
@@ -354,11 +331,11 @@ extern "C" __global__ void __launch_bounds__(FF_SEG_THREADS)
 fa_seg_bounds_i32(const int* ids, int* bounds, int S) {
   ff_seg_bounds(ids, bounds, S);
 }
-// fa_fwd_bf16 with the packed-document mask.  Resources (hipcc -O3
-// --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage): 240 VGPRs, 0
-// AGPRs, 64 KiB LDS, scratch 0, no spills, 2 waves/SIMD (fa_fwd_bf16: 242, the
-// rest equal); the pre-pass 18 VGPRs, 1 KiB LDS, 8 waves/SIMD.
-extern "C" __global__ void __launch_bounds__(FF_THREADS, 2)
+// fa_fwd_bf16 with the packed-document mask.  Resources (the extension's flags,
+// -Rpass-analysis=kernel-resource-usage): 204 VGPRs, 0 AGPRs, 64 KiB LDS,
+// scratch 0, no spills, 2 waves/SIMD (fa_fwd_bf16: 203, the rest equal); the
+// pre-pass 18 VGPRs, 1 KiB LDS, 8 waves/SIMD.
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FF_THREADS, 2)
 fa_fwd_seg_bf16(const unsigned short* q, const unsigned short* k,
                 const unsigned short* v, unsigned short* out, float* lse,
                 const int* bounds, int B, int Hq, int Hkv, int S, float scale,

@@ -1001,6 +1001,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma32_probe", &mfma32_probe);
   m.def("tr_probe", &tr_probe);
   m.def("_relayout_probe", &relayout_probe, pybind11::arg("x"));
+  m.def("_stage_probe", &stage_probe, pybind11::arg("x"), pybind11::arg("threads"));
   m.def("philox_uniform_", &philox_fill<false>);
   m.def("philox_normal_", &philox_fill<true>);
   m.def("philox_dropout", &philox_dropout);

@@ -10,6 +10,12 @@
 #include "fa32_lds_map.h"
 
 #define FF_D 128
+// Attribute of the kernels built on the direct staging below (forward, fa2_dq,
+// fa2_dv / fa2_dk, the staging probe): compiled without the packed fp32 VALU
+// ops (v_pk_{add,mul,fma}_f32); the scalar forms give the same bits.  Per
+// kernel, not a build flag: every other kernel of the extension is compiled as
+// before.  NOTES_FA32_STAGING.md has each kernel's time with and without it.
+#define FF_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
 #define FF_LOG2E 1.44269504088896340736f
 #define FF_LN2 0.69314718055994530942f
 
@@ -135,6 +141,72 @@ DEV void ff_stage_rows(const unsigned short* __restrict__ g, int stride, unsigne
     const int ge = (e / FF_D) * stride + (e % FF_D);
     ff_chunk_store(ff_chunk_load(g, ge), l, e);
   }
+}
+
+// The direct sibling of ff_stage_rows: the same tile, the same LDS image byte
+// for byte, moved by global_load_lds_dwordx4 (16 bytes per lane, global -> LDS
+// with no destination VGPR and no ds_write).  The LDS side of that load is
+// linear (M0 = wave-uniform base, lane l lands at base + 16*l), so the swizzle
+// sits on the source address: fa32_lds_map.h, "the SOURCE side".
+// ASYNCHRONOUS: the call only issues the FF_ASYNC_LOADS(ROWS, THREADS) loads of
+// this thread.  A tile is readable once every wave has passed ff_stage_wait()
+// (its own loads have landed in LDS) and then a __syncthreads() of the
+// kernel's (the other waves' have): the order gemm8.hip keeps, drain then
+// barrier.  No barrier in here (README rule 3), and the caller keeps every wave
+// of the block issuing, active or not: a wave that skips the call leaves its
+// pieces of the tile stale.
+// Inline asm, where gemm8.hip uses __builtin_amdgcn_global_load_lds: behind the
+// builtin the compiler's wait-count pass treats every later LDS read as a
+// reader of the pending load (it cannot tell the two buffers apart) and puts
+// s_waitcnt vmcnt(0) in front of the first ds_read of the tile being computed,
+// which is the wait the prefetch exists to avoid.  The asm keeps the load out
+// of that scoreboard; ff_stage_wait is then the ONLY thing that orders it (rule
+// 2's concern, with LDS as the destination: nothing may read the buffer before
+// the wait and the barrier, and the "memory" clobbers keep the compiler from
+// moving an LDS access across either statement).  The compiler's own counted
+// vmcnt waits stay correct: the counter retires in order, so an unknown load
+// in flight can only make one of them wait longer.  s_nop: one wait state
+// between the SALU write of M0 and the load that reads it (at issue, so M0 is
+// restored right behind it).
+// One source offset per thread: the row of load i is (tid >> 4) + i *
+// THREADS/16, THREADS/16 is a multiple of 16, the period of the swizzle, so
+// load i reads ff_map_async_step further on.  The instruction offset stays 0
+// (it would move the LDS side as well).
+#define FF_ASYNC_LOADS(ROWS, THREADS) ((ROWS) * FF_MAP_ROW_BYTES / ((THREADS) * 16))
+template <int ROWS, int THREADS>
+DEV void ff_stage_async(const unsigned short* __restrict__ g, int stride, unsigned short* l,
+                        int tid) {
+  static_assert(THREADS % 256 == 0 && (ROWS * FF_MAP_ROW_BYTES) % (THREADS * 16) == 0,
+                "whole 1 KiB pieces per wave, rows of later loads a multiple of 16 further");
+  const int voff0 = ff_map_async_src(0, tid, THREADS, stride) * 2;  // bytes, >= 0
+  const unsigned lbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)l;
+#pragma unroll
+  for (int i = 0; i < FF_ASYNC_LOADS(ROWS, THREADS); ++i) {
+    // the step goes into the 32-bit lane offset (one v_add), not into a scalar
+    // base per load: 8 more 64-bit bases live across the forward's loop spill
+    // SGPRs
+    const int voff = voff0 + i * ff_map_async_step(THREADS, stride) * 2;
+    const unsigned m0 =
+        __builtin_amdgcn_readfirstlane(lbase + ff_map_async_base(i, tid, THREADS));
+    unsigned keep;  // M0 is the compiler's: handed back as found
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %3\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, %2\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(g), "s"(m0)
+        : "memory");
+  }
+}
+// Every direct load (and every other vector load) of this wave has landed:
+// s_waitcnt vmcnt(0), expcnt and lgkmcnt left at "no wait".  The builtin also
+// tells the compiler's wait-count pass that its own scoreboard is clean here;
+// the empty asm keeps LDS accesses on their side of the wait.
+DEV void ff_stage_wait() {
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  asm volatile("" ::: "memory");
 }
 
 // A-operand fragment: rows s2*32 + l31 of a swizzled [*x128] LDS tile,

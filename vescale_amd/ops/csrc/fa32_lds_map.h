@@ -67,3 +67,43 @@ FF_MAP_FN int ff_map_tr(int ds, int l15, int l31, int half, int jj) {
 // ff_map_chunk(j, tid, threads), stored at byte ff_map_chunk_byte(e)
 FF_MAP_FN int ff_map_chunk(int j, int tid, int threads) { return (tid + j * threads) * 8; }
 FF_MAP_FN int ff_map_chunk_byte(int e) { return ff_map_swz(e * 2); }
+
+// ---------------------------------------------------------------------------
+// The SOURCE side of the same image, for direct global -> LDS loads
+// (global_load_lds, 16 bytes per lane, no destination VGPR; ff_stage_async in
+// fa32_common.h).  Such a load cannot scatter: one load of one wave fills 1 KiB
+// of LINEAR LDS, lane l at base + 16*l, which is 4 whole tile rows.  So the
+// swizzle moves to the address the lane reads FROM: the lane that fills the
+// 16-byte position p of the image (byte 16*p) fetches the chunk that lives
+// there.  ff_map_swz is an involution (it XORs bits 4-7 with a function of the
+// bits above them), so that chunk is at byte ff_map_swz(16*p) of the row-major
+// tile; the XOR permutes the 16 slots of one 256-byte row, so the 16 lanes of
+// a quarter-wave still read one whole row and the global side stays coalesced.
+//
+// Positions to lanes: the tile is cut into 1 KiB pieces; wave w of W =
+// threads/64 waves takes pieces w, w + W, w + 2W, ..., one load each.  Load i
+// of thread tid (lane l = tid & 63 of wave w = tid >> 6) is piece w + i*W,
+// position (w + i*W)*64 + l = tid + i*threads: ff_map_chunk's assignment in
+// 16-byte units, so the direct path moves the same chunk per (i, tid) as the
+// register path and only the place of the swizzle differs.
+// ---------------------------------------------------------------------------
+#define FF_MAP_PIECE_BYTES 1024  // one direct load of one wave: 64 lanes x 16 bytes
+
+// byte offset, in the row-major [rows][128] tile, of the chunk at image position p
+FF_MAP_FN int ff_map_src_byte(int p) { return ff_map_swz(16 * p); }
+// image position that load i of thread tid fills
+FF_MAP_FN int ff_map_async_pos(int i, int tid, int threads) { return tid + i * threads; }
+// LDS byte offset of the wave-uniform base of that load (the lane adds 16*l)
+FF_MAP_FN int ff_map_async_base(int i, int tid, int threads) {
+  return ((tid >> 6) + i * (threads >> 6)) * FF_MAP_PIECE_BYTES;
+}
+// element offset that load reads from, in a tile whose rows are `stride`
+// elements apart in global memory (stride = FF_MAP_D: a contiguous tile)
+FF_MAP_FN int ff_map_async_src(int i, int tid, int threads, int stride) {
+  const int b = ff_map_src_byte(ff_map_async_pos(i, tid, threads));
+  return (b >> 8) * stride + ((b & (FF_MAP_ROW_BYTES - 1)) >> 1);
+}
+// With threads/16 a multiple of 16 (the period of g) load i reads the rows
+// i * threads/16 below load 0's with the same XOR: src(i) = src(0) + i * step,
+// which is how ff_stage_async forms its addresses.
+FF_MAP_FN int ff_map_async_step(int threads, int stride) { return (threads >> 4) * stride; }

@@ -118,6 +118,29 @@ extern "C" __global__ void relayout_probe_kernel(const float* __restrict__ in,
   }
 }
 
+// staging probe: one block stages the same [ROWS][128] tile (rows `stride`
+// elements apart) twice, by the register path (ff_stage_rows) into one LDS
+// array and by the direct path (ff_stage_async, ff_stage_wait) into another,
+// and copies both images out linearly: out[0] = ff_stage_rows's, out[1] =
+// ff_stage_async's, ROWS*128 bf16 each.  The host holds them bitwise equal.
+template <int ROWS, int THREADS>
+__global__ void FF_NO_PK_F32 __launch_bounds__(THREADS)
+stage_probe_kernel(const unsigned short* __restrict__ g, int stride,
+                   unsigned short* __restrict__ out) {
+  __shared__ unsigned short la[ROWS * FF_D];
+  __shared__ unsigned short lb[ROWS * FF_D];
+  const int tid = threadIdx.x;
+  ff_stage_async<ROWS, THREADS>(g, stride, lb, tid);
+  ff_stage_rows<ROWS, THREADS>(g, stride, la, tid);
+  ff_stage_wait();
+  __syncthreads();
+  for (int e = tid * 8; e < ROWS * FF_D; e += THREADS * 8) {
+    *reinterpret_cast<ff_shortx8*>(out + e) = *reinterpret_cast<const ff_shortx8*>(la + e);
+    *reinterpret_cast<ff_shortx8*>(out + ROWS * FF_D + e) =
+        *reinterpret_cast<const ff_shortx8*>(lb + e);
+  }
+}
+
 namespace {
 
 at::Tensor probe_out(at::IntArrayRef sizes, at::ScalarType dtype) {
@@ -148,6 +171,31 @@ at::Tensor relayout_probe(at::Tensor x) {
   b.arg("x", x, F32, {64, 32});
   auto out = at::empty({2, 64, 4, 8}, x.options().dtype(at::kShort));  // on x's device
   b.launch(relayout_probe_kernel, 1, 64, x.data_ptr<float>(), bf16_mut(out));
+  return out;
+}
+
+// x: [rows, stride] bf16, rows in {64, 256}, stride a positive multiple of 128
+// (the tile is columns 0..127 of every row); threads in {256, 512}
+// -> [2 (ff_stage_rows, ff_stage_async), rows, 128] LDS images as bf16 bits
+at::Tensor stage_probe(at::Tensor x, int64_t threads) {
+  Binding b("_stage_probe", "x", x);
+  b.arg("x", x, BF16, {-1, -1});
+  const int64_t rows = x.size(0), stride = x.size(1);
+  TORCH_CHECK(rows == 64 || rows == 256, b.fn, ": rows = ", rows, " must be 64 or 256");
+  TORCH_CHECK(stride >= FF_D && stride % FF_D == 0 && stride <= (1 << 16), b.fn, ": stride = ",
+              stride, " must be a multiple of 128 in [128, 65536]");
+  TORCH_CHECK(threads == 256 || threads == 512, b.fn, ": threads = ", threads,
+              " must be 256 or 512");
+  auto out = at::empty({2, rows, FF_D}, x.options().dtype(at::kShort));
+  const int st = (int)stride;
+  if (rows == 64 && threads == 256)
+    b.launch(stage_probe_kernel<64, 256>, 1, 256, bf16(x), st, bf16_mut(out));
+  else if (rows == 64)
+    b.launch(stage_probe_kernel<64, 512>, 1, 512, bf16(x), st, bf16_mut(out));
+  else if (threads == 256)
+    b.launch(stage_probe_kernel<256, 256>, 1, 256, bf16(x), st, bf16_mut(out));
+  else
+    b.launch(stage_probe_kernel<256, 512>, 1, 512, bf16(x), st, bf16_mut(out));
   return out;
 }
 
