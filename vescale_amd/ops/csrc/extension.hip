@@ -13,6 +13,7 @@
 #include "rmsnorm.hip"
 #include "rope.hip"
 #include "rope_qkv.hip"
+#include "transpose.hip"
 #include "swiglu.hip"
 #include "adamw.hip"
 #include "cross_entropy.hip"
@@ -335,7 +336,12 @@ at::Tensor swiglu_packed_fwd(at::Tensor gu) {
   return out;
 }
 
-at::Tensor swiglu_packed_bwd(at::Tensor dy, at::Tensor gu) {
+// transposed: also returns dgu^T [2F, rows] (a second output of the same
+// pass, swiglu_packed_bwd_t_bf16): {dgu, dgut}.  Without it, dgu alone from
+// the kernel that has always computed it.
+std::variant<at::Tensor, std::vector<at::Tensor>> swiglu_packed_bwd(at::Tensor dy,
+                                                                    at::Tensor gu,
+                                                                    bool transposed) {
   Binding b("swiglu_packed_bwd", "dy", dy);
   int F = (int)b.last_dim("packed ffn dim F2 (gu.size(-1))", gu, 16) / 2;
   auto sizes = gu.sizes().vec();
@@ -343,10 +349,23 @@ at::Tensor swiglu_packed_bwd(at::Tensor dy, at::Tensor gu) {
   b.arg("dy", dy, BF16, at::IntArrayRef(sizes));
   b.arg("gu", gu, BF16);
   int64_t rows = gu.numel() / (2 * F);
+  if (!transposed) {
+    auto dgu = at::empty_like(gu);
+    b.launch(swiglu_packed_bwd_bf16, grid_for(rows * (F / 8), 256), 256, bf16(dy),
+             bf16(gu), bf16_mut(dgu), rows, F);
+    return dgu;
+  }
+  // 16-byte transposed stores need whole 8-row chunks; a tile's elements are
+  // indexed in int and F / 64 is a grid.y
+  TORCH_CHECK(rows % 8 == 0 && rows < (1 << 24) && F < (1 << 22), b.fn,
+              ": transposed=True needs rows (gu.numel() / F2) = ", rows,
+              " to be a multiple of 8 below 2^24 and F below 2^22");
   auto dgu = at::empty_like(gu);
-  b.launch(swiglu_packed_bwd_bf16, grid_for(rows * (F / 8), 256), 256, bf16(dy),
-           bf16(gu), bf16_mut(dgu), rows, F);
-  return dgu;
+  auto dgut = at::empty({2 * (int64_t)F, rows}, gu.options());
+  if (rows == 0) return std::vector<at::Tensor>{dgu, dgut};
+  b.launch(swiglu_packed_bwd_t_bf16, dim3((unsigned)((rows + 63) / 64), (unsigned)((F + 63) / 64)),
+           256, bf16(dy), bf16(gu), bf16_mut(dgu), bf16_mut(dgut), (int)rows, F);
+  return std::vector<at::Tensor>{dgu, dgut};
 }
 
 // ------------------------------ Cross entropy ------------------------------
@@ -582,12 +601,46 @@ at::Tensor gemm_grouped(const Binding& b, const at::Tensor& a, const Weights& ws
   return out;
 }
 
+// ------------------------------ GEMM operand preparation -------------------
+// group_form = "transpose" of gemm_tn8: a [R,C] -> a^T [C,R] as a contiguous
+// tensor (transpose.hip), the copy that hands the library a wgrad operand
+// contiguous along the contraction.  It is no product: b must be the empty
+// list.  mode picks the tile: 0 = 128 x 128 (the faster one, profiles/
+// wgrad_transposed_ab.txt), 1 = 64 x 64 (kept for that A/B).
+at::Tensor gemm_operand_t(const Binding& b, const at::Tensor& a, const Weights& bw,
+                          int64_t mode) {
+  const auto* list = std::get_if<std::vector<at::Tensor>>(&bw);
+  TORCH_CHECK(list && list->empty(), b.fn,
+              ": group_form = 'transpose' takes one operand: b must be []");
+  TORCH_CHECK(mode == 0 || mode == 1, b.fn, ": group_form = 'transpose' has mode 0 or 1, got ",
+              mode);
+  TORCH_CHECK(a.dim() == 2, b.fn, ": argument 'a' of group_form = 'transpose' must be [R,C], ",
+              "got sizes=", a.sizes());
+  const int64_t R = a.size(0), C = a.size(1);
+  TORCH_CHECK(R % 8 == 0 && C % 8 == 0, b.fn, ": argument 'a' of group_form = 'transpose' needs ",
+              "R % 8 == 0 and C % 8 == 0, got sizes=", a.sizes());
+  // a tile's elements are indexed in int (128 rows of R or C elements) and
+  // C / tile is a grid.y
+  TORCH_CHECK(R < (1 << 24) && C < (1 << 22), b.fn, ": argument 'a' of group_form = ",
+              "'transpose' needs R < 2^24 and C < 2^22, got sizes=", a.sizes());
+  b.arg("a", a, BF16);
+  gemm_grouped_aligned(b, "a", a);
+  auto out = at::empty({C, R}, a.options());
+  if (R == 0 || C == 0) return out;
+  const int t = mode == 0 ? 128 : 64;
+  b.launch(mode == 0 ? transpose_bf16 : transpose_t64_bf16,
+           dim3((unsigned)((R + t - 1) / t), (unsigned)((C + t - 1) / t)), TP_THREADS, bf16(a),
+           bf16_mut(out), (int)R, (int)C);
+  return out;
+}
+
 at::Tensor gemm_tn8(at::Tensor a, Weights bw, int64_t mode, OptTensor group_offsets,
                     std::string group_form, OptTensor group_x, OptTensor group_out) {
   // via the 8-phase 256x256 template (gemm8.hip); with group_form, the
   // grouped expert forms (gemm_grouped.hip)
   Binding bd("gemm_tn8", "a", a);
   TORCH_CHECK(mode >= 0 && mode <= 8, "gemm_tn8: mode = ", mode, " must be in 0..8");
+  if (group_form == "transpose") return gemm_operand_t(bd, a, bw, mode);
   if (!group_form.empty() || group_offsets.has_value() || group_x.has_value() ||
       group_out.has_value())
     return gemm_grouped(bd, a, bw, group_offsets, group_form, group_x, group_out);
@@ -963,7 +1016,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("swiglu_packed_fwd", &swiglu_packed_fwd);
-  m.def("swiglu_packed_bwd", &swiglu_packed_bwd);
+  m.def("swiglu_packed_bwd", &swiglu_packed_bwd, pybind11::arg("dy"), pybind11::arg("gu"),
+        pybind11::arg("transposed") = false);
   m.def("ce_fwd", &ce_fwd, pybind11::arg("logits"), pybind11::arg("target"),
         pybind11::arg("ignore_index"), pybind11::arg("vocab_start") = 0,
         pybind11::arg("vocab_total") = -1);

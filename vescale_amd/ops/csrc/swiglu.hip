@@ -5,10 +5,11 @@
 // gate/up are separate [N, F] bf16 tensors (the two halves of the fused
 // w13 matmul output views).
 #include "common.h"
+#include "transpose.hip"  // tp_lds_put / tp_lds_get_t
 
 #define BLOCK 256
 
-// dup = dy * silu(gate), taken as (dy * gate) * sig by all four sites below
+// dup = dy * silu(gate), taken as (dy * gate) * sig by all five sites below
 // (so the packed and the separate kernels agree bitwise).  Where dy * gate
 // overflows fp32 while silu(gate) is still small or 0 (gate -3e38, dy 1e18:
 // inf * 0 = NaN) the product is taken as dy * (gate * sig) instead.
@@ -74,6 +75,69 @@ swiglu_packed_bwd_bf16(const unsigned short* __restrict__ dy,
     unsigned short* dbase = dgu + row * 2 * F;
     *reinterpret_cast<short8v*>(dbase + col) = og;
     *reinterpret_cast<short8v*>(dbase + F + col) = ou;
+  }
+}
+
+// swiglu_packed_bwd_bf16 with a second, TRANSPOSED output dgut [2F, n_rows]
+// (the contraction-contiguous dy operand of the w13 wgrad GEMM) written from
+// the values the block already holds: no extra read, and dgu gets the same
+// values from the same expressions as above.  A block owns a 64 x 64 tile of
+// dgate and the same tile of dup, stores both row-major, and passes them
+// through the LDS image of transpose.hip (conflict-free there) for the
+// 16-byte transposed stores.  n_rows % 8 == 0; partial tiles are predicated
+// per chunk and every thread reaches the barrier.  32-bit indexing inside a
+// tile, 64-bit tile bases.  grid = (ceil(n_rows/64), ceil(F/64)).
+extern "C" __global__ void TP_NO_PK_F32 __launch_bounds__(BLOCK)
+swiglu_packed_bwd_t_bf16(const unsigned short* __restrict__ dy,
+                         const unsigned short* __restrict__ gu,
+                         unsigned short* __restrict__ dgu,
+                         unsigned short* __restrict__ dgut,
+                         int n_rows, int F) {
+  constexpr int TT = 64, PER = TT * TT / 8 / BLOCK, CPR = TT / 8;
+  __shared__ __attribute__((aligned(16))) unsigned char lds_g[TT * TT * 2];
+  __shared__ __attribute__((aligned(16))) unsigned char lds_u[TT * TT * 2];
+  const int r0 = blockIdx.x * TT, c0 = blockIdx.y * TT;
+  const int rows = min(TT, n_rows - r0), cols = min(TT, F - c0);
+  const unsigned short* dyb = dy + ((int64_t)r0 * F + c0);
+  const unsigned short* gub = gu + ((int64_t)r0 * 2 * F + c0);
+  unsigned short* dgub = dgu + ((int64_t)r0 * 2 * F + c0);
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const int q = threadIdx.x + j * BLOCK;
+    const int r = q / CPR, c = (q % CPR) * 8;
+    short8v og = {}, ou = {};
+    if (r < rows && c < cols) {
+      short8v d = *reinterpret_cast<const short8v*>(dyb + (r * F + c));
+      short8v g = *reinterpret_cast<const short8v*>(gub + (r * 2 * F + c));
+      short8v u = *reinterpret_cast<const short8v*>(gub + (r * 2 * F + F + c));
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float df = bf16_to_f32((unsigned short)d[e]);
+        float gf = bf16_to_f32((unsigned short)g[e]);
+        float uf = bf16_to_f32((unsigned short)u[e]);
+        float sig = 1.0f / (1.0f + __expf(-gf));
+        og[e] = (short)f32_to_bf16(df * uf * sig * (1.0f + gf * (1.0f - sig)));
+        ou[e] = (short)f32_to_bf16(swiglu_dup(df, gf, sig));
+      }
+      *reinterpret_cast<short8v*>(dgub + (r * 2 * F + c)) = og;
+      *reinterpret_cast<short8v*>(dgub + (r * 2 * F + F + c)) = ou;
+    }
+    tp_lds_put<TT>(lds_g, q, og);
+    tp_lds_put<TT>(lds_u, q, ou);
+  }
+  __syncthreads();
+  unsigned short* tg = dgut + ((int64_t)c0 * n_rows + r0);
+  unsigned short* tu = dgut + ((int64_t)(F + c0) * n_rows + r0);
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const int q = threadIdx.x + j * BLOCK;
+    const int c = q / CPR, r = (q % CPR) * 8;
+    const short8v g = tp_lds_get_t<TT>(lds_g, q);
+    const short8v u = tp_lds_get_t<TT>(lds_u, q);
+    if (c < cols && r < rows) {
+      *reinterpret_cast<short8v*>(tg + (c * n_rows + r)) = g;
+      *reinterpret_cast<short8v*>(tu + (c * n_rows + r)) = u;
+    }
   }
 }
 

@@ -287,14 +287,20 @@ def swiglu(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
 
 
 class _SwiGLUPacked(torch.autograd.Function):
-    """gu = [.., 2F] (gate||up) -> [.., F]; avoids split+cat round trips."""
+    """gu = [.., 2F] (gate||up) -> [.., F]; avoids split+cat round trips.
+
+    want_t: the producer of gu is a dense linear whose wgrad takes dgu^T
+    (linear() marks its output, see _WGRAD_T).  The backward then asks the
+    kernel for dgu^T as a second output of the same pass and hands it over
+    as an attribute of dgu; _LinearWgrad.backward takes it off again."""
 
     @staticmethod
-    def forward(ctx, gu: torch.Tensor):
+    def forward(ctx, gu: torch.Tensor, want_t: bool = False):
         if _use_hip(gu):
             g = gu.contiguous()
             ctx.save_for_backward(g)
             ctx.hip = True
+            ctx.want_t = want_t
             return _ext().swiglu_packed_fwd(g)
         ctx.save_for_backward(gu)
         ctx.hip = False
@@ -306,7 +312,11 @@ class _SwiGLUPacked(torch.autograd.Function):
     def backward(ctx, dy: torch.Tensor):
         (gu,) = ctx.saved_tensors
         if ctx.hip:
-            return _ext().swiglu_packed_bwd(dy.contiguous(), gu)
+            if ctx.want_t and (gu.numel() // gu.shape[-1]) % 8 == 0:
+                dgu, dgut = _ext().swiglu_packed_bwd(dy.contiguous(), gu, transposed=True)
+                setattr(dgu, _WGRAD_T, dgut)
+                return dgu, None
+            return _ext().swiglu_packed_bwd(dy.contiguous(), gu), None
         F = gu.shape[-1] // 2
         g = gu[..., :F].float()
         u = gu[..., F:].float()
@@ -314,11 +324,11 @@ class _SwiGLUPacked(torch.autograd.Function):
         sig = torch.sigmoid(g)
         dgate = d * u * sig * (1 + g * (1 - sig))
         dup = _swiglu_dup(d, g, sig)
-        return torch.cat([dgate, dup], dim=-1).to(gu.dtype)
+        return torch.cat([dgate, dup], dim=-1).to(gu.dtype), None
 
 
 def swiglu_packed(gu: torch.Tensor) -> torch.Tensor:
-    return _SwiGLUPacked.apply(gu)
+    return _SwiGLUPacked.apply(gu, getattr(gu, _WGRAD_WANTS_T, False))
 
 
 # ---------------------------------------------------------------------------
@@ -893,11 +903,16 @@ def scale_flat_(x: torch.Tensor, scale) -> None:
 # Linear (in-tree CDNA4 GEMM path)
 # ---------------------------------------------------------------------------
 # VESCALE_GEMM selects the nn.Linear GEMM backend:
-#   "blaslt" (default) — torch.matmul -> hipBLASLt Tensile assembly kernels.
+#   "blaslt" (default) — torch.matmul -> hipBLASLt Tensile assembly kernels;
+#                        forward and dgrad as F.linear issues them, wgrad in
+#                        the operand layout _wgrad_form picks per shape, its
+#                        transposed operands made by ops/csrc/transpose.hip.
 #   "gemm8"            — the in-tree 256x256 8-phase MFMA kernel
 #                        (ops/csrc/gemm8.hip, rot3np schedule) for the
-#                        forward and dgrad GEMMs; wgrad (both operands
-#                        contraction-major) stays on the library: the
+#                        forward and dgrad GEMMs; its wgrad is the library's
+#                        dy.t() @ x, form (a) of the wgrad forms below (the
+#                        layout rule of linear() belongs to the blaslt
+#                        backend): the
 #                        contraction-major kernels that exist now are the
 #                        grouped expert forms below (gemm_grouped.hip, dgrad
 #                        and wgrad staged transposed into LDS), which serve
@@ -919,7 +934,8 @@ def _g8_ok(m: int, n: int, k: int) -> bool:
 class _Linear8(torch.autograd.Function):
     """y = x @ w^T via the in-tree TN kernel; dgrad = gemm_tn(dy, w^T)
     (one cheap [N,K]->[K,N] transpose per backward — arithmetic intensity
-    of the GEMM is ~4 orders above the copy); wgrad on the library."""
+    of the GEMM is ~4 orders above the copy); wgrad is the library's
+    dy.t() @ x (form "a" of WGRAD_FORMS)."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, w: torch.Tensor):
@@ -950,14 +966,129 @@ class _Linear8(torch.autograd.Function):
                 dx = dys @ w
             dx = dx.reshape(x.shape)
         if ctx.needs_input_grad[1]:
-            dw = dys.t() @ x2  # library wgrad (see header note)
+            dw = dys.t() @ x2  # library wgrad, form "a" (see header note)
         return dx, dw
 
 
+# ---------------------------------------------------------------------------
+# Dense wgrad in the library's fast operand layout (NOTES_WGRAD_LAYOUT.md)
+# ---------------------------------------------------------------------------
+# dw [N,K] = dy^T [N,M] . x [M,K].  autograd's F.linear hands the library
+# dy.t() @ x, both operands strided along the contraction M, the layout class
+# the library runs slowest.  The same product in other operand layouts, the
+# transposed operands made by the streaming transposing copy of
+# ops/csrc/transpose.hip (or, for dy of w13, written by swiglu_packed_bwd as a
+# second output):
+#   "a"  dy.t() @ x          the form of F.linear's autograd
+#   "b"  dyT @ x             dyT = dy^T contiguous [N,M]
+#   "c"  dyT @ xT.t()        and xT = x^T contiguous [K,M]: both operands
+#                            contiguous along the contraction, the forward's class
+#   "d"  (xT @ dy)^T         the [K,N] result transposed by the same copy
+WGRAD_FORMS = ("a", "b", "c", "d")
+
+# side channel between _LinearWgrad and _SwiGLUPacked: the linear's output
+# carries _WGRAD_WANTS_T, the gradient that comes back carries its transpose
+_WGRAD_WANTS_T = "_vescale_wgrad_wants_t"
+_WGRAD_T = "_vescale_wgrad_t"
+
+
+def _wgrad_form(m: int, n: int, k: int) -> str:
+    """The static rule: which form the wgrad of a [M,K] x [N,K]^T linear takes.
+    Shapes only: no timing, no table read at run time, so two runs of one
+    build issue the same calls.
+
+    From profiles/wgrad_layout_ab.txt (M = 32768): the library runs (c) at
+    1.4-1.6 PF/s where (a) runs at 1.0-1.2, but the transposes of dy [M,N] and
+    x [M,K] cost what they move, so the change pays only where the output is
+    wide against the contraction-free width of x: N >= 4K, and where dy^T is
+    an affordable transient (at most 2 GiB).  That is w13: 6.4 -> 4.8 ms + 0.12
+    for x^T + 0.35 in swiglu_packed_bwd for dy^T, and there the library's (c)
+    kernel sums in the order of its (a) kernel: dw keeps its bits
+    (profiles/wgrad_layout_bits.txt).  Below N = 4K (wqkv, wo, w2) no form
+    beats (a) by more than its transposes cost.  The LM head (dy^T 8.4 GB)
+    stays on (a) too: (d) would save 3 ms per step there, but the library's
+    kernels for that shape sum in another order, a few dw elements in 10^5
+    change, and the training run no longer reproduces the earlier one."""
+    if m >= 4096 and n >= 4 * k and 2 * m * n <= 2 ** 31:
+        return "c"
+    return "a"
+
+
+def _transposed(t: torch.Tensor) -> torch.Tensor:
+    """t [R,C] bf16 -> t^T as a contiguous [C,R] (ops/csrc/transpose.hip)."""
+    return _ext().gemm_tn8(t.contiguous(), [], 0, group_form="transpose")
+
+
+def _wgrad_fits(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """What the transposing copy takes: bf16 on the GPU, every extent a
+    multiple of 8 (16-byte chunks on both sides)."""
+    m = x.numel() // x.shape[-1] if x.shape[-1] else 0
+    return (
+        x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+        and w.dim() == 2 and x.dim() >= 2 and x.shape[-1] == w.shape[1]
+        and m > 0 and m % 8 == 0 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0
+        and _use_hip(x, w)
+    )
+
+
+class _LinearWgrad(torch.autograd.Function):
+    """y = x @ w^T and dx = dy @ w are the library calls of F.linear and its
+    autograd, so both keep their bits; dw takes `form`.  Nothing beyond x and
+    w is saved, and every transposed operand dies in backward."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, w: torch.Tensor, form: str):
+        ctx.save_for_backward(x, w)
+        ctx.form = form
+        return torch.nn.functional.linear(x, w)
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        x, w = ctx.saved_tensors
+        n, k = w.shape
+        dys = dy.reshape(-1, n)
+        x2 = x.reshape(-1, k)
+        dyt = getattr(dy, _WGRAD_T, None)
+        if dyt is not None:
+            delattr(dy, _WGRAD_T)
+            if dyt.shape != (n, dys.shape[0]):
+                dyt = None
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = (dys @ w).reshape(x.shape)
+        if ctx.needs_input_grad[1]:
+            form = ctx.form
+            if form in ("b", "c") and dyt is None:
+                dyt = _transposed(dys)
+            if form == "b":
+                dw = dyt @ x2
+            elif form == "c":
+                dw = dyt @ _transposed(x2).t()
+            elif form == "d":
+                dw = _transposed(_transposed(x2) @ dys)
+            else:
+                dw = dys.t() @ x2
+        return dx, dw, None
+
+
 def linear(x: torch.Tensor, w: torch.Tensor,
-           bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+           bias: Optional[torch.Tensor] = None, *, _wgrad_form_override: Optional[str] = None,
+           ) -> torch.Tensor:
+    """F.linear; on the default backend, for bf16 GPU tensors without bias,
+    with the wgrad product in the operand layout _wgrad_form picks for the
+    shape.  _wgrad_form_override (tests, tools/wgrad_layout_ab.py) forces a
+    form of WGRAD_FORMS."""
     if _gemm_backend() == "gemm8" and bias is None:
         return _Linear8.apply(x, w)
+    if bias is None and x.is_cuda and _wgrad_fits(x, w):
+        form = _wgrad_form_override or _wgrad_form(x.numel() // x.shape[-1], *w.shape)
+        if form not in WGRAD_FORMS:
+            raise ValueError(f"wgrad form must be one of {WGRAD_FORMS}, got {form!r}")
+        if form != "a" or _wgrad_form_override:
+            y = _LinearWgrad.apply(x, w, form)
+            if form in ("b", "c"):
+                setattr(y, _WGRAD_WANTS_T, True)
+            return y
     return torch.nn.functional.linear(x, w, bias)
 
 
