@@ -60,6 +60,10 @@ class LlamaConfig:
     # lets attention take the tuned D=128 kernels with their run mask
     # (ops.flash_attention, contiguous_segments)
     contiguous_segments: bool = False
+    # Mistral-style local attention: a token sees itself and the W - 1 tokens
+    # before it (ops.flash_attention, window=(W - 1, 0)); None: full causal.
+    # MixtralConfig inherits the field
+    sliding_window: Optional[int] = None
 
     @property
     def head_dim(self) -> int:
@@ -111,6 +115,8 @@ class Attention(nn.Module):
         self.cfg = cfg
         self.tp = tp or TPContext.single()
         assert cfg.n_heads % self.tp.world == 0 and cfg.n_kv_heads % self.tp.world == 0
+        if cfg.sliding_window is not None and cfg.sliding_window < 1:
+            raise ValueError(f"sliding_window must be >= 1, got {cfg.sliding_window}")
         self.hq = cfg.n_heads // self.tp.world
         self.hkv = cfg.n_kv_heads // self.tp.world
         d, hd = cfg.dim, cfg.head_dim
@@ -142,7 +148,14 @@ class Attention(nn.Module):
         qkv = self.wqkv(x)
         # rope_qkv emits [B, H, S, D] directly (attention's native layout)
         q, k, v = rope_qkv(qkv, rope_table, self.hq, self.hkv, cfg.head_dim)
-        if segment_ids is None:
+        if cfg.sliding_window is not None:
+            # band mask: the general HIP kernel's windowed variant (the tuned
+            # kernels have none), with the document mask when ids are given
+            seg = {} if segment_ids is None else dict(
+                q_segment_ids=segment_ids, contiguous_segments=cfg.contiguous_segments)
+            o = flash_attention(q, k, v, is_causal=True,
+                                window=(cfg.sliding_window - 1, 0), **seg)
+        elif segment_ids is None:
             # our MFMA flash forward + library backward (ops/functional.py);
             # falls back to SDPA off-GPU or for unsupported shapes
             o = flash_attention_causal(q, k, v)

@@ -20,12 +20,30 @@
 // index arithmetic inside int.  KV (resp. Q) tiles wholly outside the
 // visible range are skipped.
 //
+// Window (band mask), the compile-time variant WIN of fwd, dkdv and dq
+// (template <int D, bool SEG, bool WIN>): key j is visible to query i iff the
+// other rules hold AND j >= i + lower, one runtime int that the host clamps to
+// [-Sq, Sk] like shift.  Only this lower diagonal bound is new on the device:
+// an upper bound is what (causal, shift) express, so the host folds a window's
+// right side into them.  The test is written once, in fg_vis<SEG, WIN>.  The
+// tile ranges follow from block-uniform scalars, with no pre-pass: a q tile at
+// q0 starts its kv loop at tile max(0, q0 + lower) / 64 (fg_kv_first; fwd and
+// dq; the end stays fg_kv_tiles, an empty range gives dead rows), and a kv
+// tile at k0 ends its q loop after the tile that holds row
+// min(Sq - 1, min(k0 + 63, Sk - 1) - lower) (fg_q_tiles; dkdv; no iteration
+// if that row is negative).  Tiles outside are never staged: the work is
+// O(S * W), not O(S^2).  WIN composes with SEG: the overlap skip applies
+// inside the window's tile range.  The WIN = false instantiations are the
+// kernels without any of this: `lower` is a dead argument that sits in what
+// was padding of the kernel arguments, and their ISA is instruction for
+// instruction that of the build before the window.
+//
 // Segment mask (packed documents), the compile-time variant SEG of fwd, dkdv
-// and dq (template <int D, bool SEG>; preprocess needs nothing): with
+// and dq (preprocess needs nothing): with
 // q_seg [B,Sq] and kv_seg [B,Sk] (int32), key j is visible to query i iff
 // kv_seg[b,j] == q_seg[b,i] AND the rule above holds.  Ids are compared for
 // equality only: no value is special and they need not be sorted.  The test
-// is written once, in fg_vis<SEG>.  fa_gen_seg_bounds_kernel writes the
+// is written once, in fg_vis<SEG, WIN>.  fa_gen_seg_bounds_kernel writes the
 // (min, max) id of every 64-row q and kv tile first; a (q tile, kv tile) pair
 // whose ranges do not overlap holds no equal pair and its whole loop
 // iteration is skipped — staging and barriers included, on block-uniform
@@ -72,6 +90,26 @@
 //   fa_gen_dkdv  64   yes  176    30     37376        2
 //   fa_gen_dkdv  128  yes  248    40     55808        1
 //   fa_gen_seg_bounds      8      0      0            8
+//   kernel       D    SEG  WIN  VGPRs  AGPRs  LDS B/block  waves/SIMD
+//   fa_gen_fwd   64   -    yes  101    16     27648        4
+//   fa_gen_fwd   128  -    yes  146    32     45056        2
+//   fa_gen_dq    64   -    yes  120    32     27648        3
+//   fa_gen_dq    128  -    yes  142    56     45056        2
+//   fa_gen_dkdv  64   -    yes  150    44     37376        2
+//   fa_gen_dkdv  128  -    yes  182    80     55808        1
+//   fa_gen_fwd   64   yes  yes  118    20     27648        3
+//   fa_gen_fwd   128  yes  yes  151    48     45056        2
+//   fa_gen_dq    64   yes  yes  132    28     27648        3
+//   fa_gen_dq    128  yes  yes  170    40     45056        2
+//   fa_gen_dkdv  64   yes  yes  176    30     37376        2
+//   fa_gen_dkdv  128  yes  yes  229    40     55808        1
+// The WIN variants keep the LDS and the occupancy of their siblings and, like
+// them, use no scratch and spill nothing.  Their rows are of the build that
+// added the window.  In that build the rows above, in their order, read
+// VGPRs (and AGPRs where those moved) 99, 154, 112, 146, 154 (44), 203
+// without SEG and 120, 161, 107 (40), 176 (40), 180, 249 with it: the same
+// figures on the build before the window and on this one, whose WIN = false
+// kernels are the same instructions (profiles/fa_gen_window.txt).
 // The segment variants hold 8 ids per lane (4 rows, 4 columns) and the tile
 // ranges; only the forward at D=64 loses a wave per SIMD (4 -> 3) to them.
 // The rows without SEG are those of the build before the segment mask.
@@ -101,6 +139,17 @@
 // The time falls with the visible share, less than in proportion.  The
 // cause was not isolated by measurement; the likely one is that a block
 // with few tiles to visit no longer amortises its prologue and epilogue.
+//
+// Measured with a window (profiles/fa_gen_window.txt; same calls and shape,
+// is_causal, median of 15, alternating samples, min-max spread 0.5%):
+//   no window: 74.12 ms, the build before the window 74.15 ms (equal within
+//   the spread; results bitwise equal)
+//   window (1023, 0): 16.07 ms (0.217x; 0.247 of the causal tile pairs visited)
+//   window (4095, 0): 53.03 ms (0.715x; 0.756 of the causal tile pairs visited)
+// Here the time falls slightly MORE than the visited share.  The cause was
+// not isolated by measurement; the likely one is that every q tile past the
+// first W / 64 now visits the same number of tiles, where the causal
+// triangle leaves the grid's last blocks the longest loops.
 #include "fa16_common.h"
 
 #include <climits>
@@ -139,7 +188,7 @@ fa_gen_seg_bounds_kernel(const int* __restrict__ q_seg,
 // ---------------------------------------------------------------------------
 // forward   grid: (ceil(Sq/64), Hq, B)
 // ---------------------------------------------------------------------------
-template <int D, bool SEG>
+template <int D, bool SEG, bool WIN>
 __global__ void __launch_bounds__(FG_THREADS)
 fa_gen_fwd_kernel(const unsigned short* __restrict__ q,
                   const unsigned short* __restrict__ k,
@@ -147,7 +196,7 @@ fa_gen_fwd_kernel(const unsigned short* __restrict__ q,
                   unsigned short* __restrict__ o,
                   float* __restrict__ lse,
                   int Hq, int Hkv, int Sq, int Sk, float scale_log2,
-                  int causal, int shift,
+                  int causal, int shift, int lower,
                   const int* __restrict__ q_seg,
                   const int* __restrict__ kv_seg,
                   const int* __restrict__ seg_bounds) {
@@ -195,7 +244,9 @@ fa_gen_fwd_kernel(const unsigned short* __restrict__ q,
     for (int r = 0; r < 4; ++r) qs[r] = fg_seg(q_seg + (int64_t)b * Sq, q0 + trow + r, Sq);
   }
   const int n_tiles = fg_kv_tiles(q0, Sq, Sk, causal, shift);
-  for (int jt = 0; jt < n_tiles; ++jt) {
+  // WIN: kv tiles wholly left of the band are skipped like the SEG ones
+  const int jt0 = WIN ? fg_kv_first(q0, lower) : 0;
+  for (int jt = jt0; jt < n_tiles; ++jt) {
     const int k0 = jt * FG_BLK;
     if constexpr (SEG) {
       // block-uniform: every wave skips the whole iteration, barriers included
@@ -223,7 +274,7 @@ fa_gen_fwd_kernel(const unsigned short* __restrict__ q,
       int col = k0 + f * 16 + (lane & 15);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float x = fg_vis<SEG>(q0 + trow + r, col, Sk, causal, shift, qs[r], ks[f])
+        float x = fg_vis<SEG, WIN>(q0 + trow + r, col, Sk, causal, shift, lower, qs[r], ks[f])
                       ? s[f][r] * scale_log2 : -INFINITY;
         s[f][r] = x;
         mx[r] = fmaxf(mx[r], x);
@@ -312,7 +363,7 @@ fa_gen_preprocess_kernel(const unsigned short* __restrict__ dout,
 // ---------------------------------------------------------------------------
 // backward 2) dK/dV   grid: (ceil(Sk/64), Hkv, B); loops the GQA group
 // ---------------------------------------------------------------------------
-template <int D, bool SEG>
+template <int D, bool SEG, bool WIN>
 __global__ void __launch_bounds__(FG_THREADS)
 fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
                    const unsigned short* __restrict__ k,
@@ -323,7 +374,7 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
                    unsigned short* __restrict__ dk,
                    unsigned short* __restrict__ dv,
                    int Hq, int Hkv, int Sq, int Sk, float scale,
-                   int causal, int shift,
+                   int causal, int shift, int lower,
                    const int* __restrict__ q_seg,
                    const int* __restrict__ kv_seg,
                    const int* __restrict__ seg_bounds) {
@@ -361,7 +412,8 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
   fg_zero(accV);
 
   const int trow = wave * 16 + 4 * (lane >> 4);   // kv tile row of acc[.][0]
-  const int n_qtiles = (Sq + FG_BLK - 1) / FG_BLK;
+  // WIN: q tiles wholly below the band are never visited
+  const int n_qtiles = WIN ? fg_q_tiles(k0, Sq, Sk, lower) : (Sq + FG_BLK - 1) / FG_BLK;
   // first q row that sees key k0: i >= k0 - shift
   const int iq_start = (causal && k0 - shift > 0) ? (k0 - shift) / FG_BLK : 0;
 
@@ -419,7 +471,8 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
         float dl = dlt_s[qc];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          bool vis = fg_vis<SEG>(q0 + qc, k0 + trow + r, Sk, causal, shift, qs[f], ks[r]);
+          bool vis = fg_vis<SEG, WIN>(q0 + qc, k0 + trow + r, Sk, causal, shift, lower, qs[f],
+                                       ks[r]);
           float p = fg_p(vis, st[f][r], scale_log2, l2);
           lpt[(trow + r) * FG_ROWS_N + qc] = f32_to_bf16(p);
           ldst[(trow + r) * FG_ROWS_N + qc] = f32_to_bf16(fg_ds(p, dpt[f][r], dl, scale));
@@ -442,7 +495,7 @@ fa_gen_dkdv_kernel(const unsigned short* __restrict__ q,
 // ---------------------------------------------------------------------------
 // backward 3) dQ   grid: (ceil(Sq/64), Hq, B)
 // ---------------------------------------------------------------------------
-template <int D, bool SEG>
+template <int D, bool SEG, bool WIN>
 __global__ void __launch_bounds__(FG_THREADS)
 fa_gen_dq_kernel(const unsigned short* __restrict__ q,
                  const unsigned short* __restrict__ k,
@@ -452,7 +505,7 @@ fa_gen_dq_kernel(const unsigned short* __restrict__ q,
                  const float* __restrict__ delta,
                  unsigned short* __restrict__ dq,
                  int Hq, int Hkv, int Sq, int Sk, float scale,
-                 int causal, int shift,
+                 int causal, int shift, int lower,
                  const int* __restrict__ q_seg,
                  const int* __restrict__ kv_seg,
                  const int* __restrict__ seg_bounds) {
@@ -505,7 +558,9 @@ fa_gen_dq_kernel(const unsigned short* __restrict__ q,
     for (int r = 0; r < 4; ++r) qs[r] = fg_seg(q_seg + (int64_t)b * Sq, q0 + trow + r, Sq);
   }
   const int n_tiles = fg_kv_tiles(q0, Sq, Sk, causal, shift);
-  for (int jt = 0; jt < n_tiles; ++jt) {
+  // WIN: kv tiles wholly left of the band are skipped like the SEG ones
+  const int jt0 = WIN ? fg_kv_first(q0, lower) : 0;
+  for (int jt = jt0; jt < n_tiles; ++jt) {
     const int k0 = jt * FG_BLK;
     if constexpr (SEG) {
       // block-uniform: every wave skips the whole iteration, barriers included
@@ -534,7 +589,7 @@ fa_gen_dq_kernel(const unsigned short* __restrict__ q,
       int col = k0 + f * 16 + (lane & 15);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        bool vis = fg_vis<SEG>(q0 + trow + r, col, Sk, causal, shift, qs[r], ks[f]);
+        bool vis = fg_vis<SEG, WIN>(q0 + trow + r, col, Sk, causal, shift, lower, qs[r], ks[f]);
         float p = fg_p(vis, s[f][r], scale_log2, l2_r[r]);
         lds_s[(trow + r) * FG_ROWS_N + f * 16 + (lane & 15)] =
             f32_to_bf16(fg_ds(p, dp[f][r], dlt_r[r], scale));

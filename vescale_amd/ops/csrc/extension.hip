@@ -817,11 +817,13 @@ std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Te
 }
 
 // ------------------------------ general-shape flash attention --------------
-struct FaGenShape { int B, Hq, Hkv, Sq, Sk, D, shift; bool seg; };
+struct FaGenShape { int B, Hq, Hkv, Sq, Sk, D, shift, lower; bool seg, win; };
+using OptInt = c10::optional<int64_t>;
 
 FaGenShape fa_gen_check(const Binding& b, const at::Tensor& q, const at::Tensor& k,
                         const at::Tensor& v, bool causal, int64_t shift,
-                        const OptTensor& q_seg, const OptTensor& kv_seg) {
+                        const OptInt& lower, const OptTensor& q_seg,
+                        const OptTensor& kv_seg) {
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
               b.fn, ": q, k, v must be [B, H, S, D]");
   int64_t D = q.size(3);
@@ -842,16 +844,21 @@ FaGenShape fa_gen_check(const Binding& b, const at::Tensor& q, const at::Tensor&
   b.arg("kv_seg", kv_seg, I32, {q.size(0), k.size(2)});  // [B, Sk]
   // clamping to [-Sq, Sk] leaves the mask j <= i + shift unchanged
   int64_t sh = std::max<int64_t>(-q.size(2), std::min<int64_t>(k.size(2), shift));
+  // the window j >= i + lower: the same clamp, for the same reasons
+  int64_t lo = std::max<int64_t>(-q.size(2), std::min<int64_t>(k.size(2), lower.value_or(0)));
   return {(int)q.size(0), (int)q.size(1), (int)k.size(1), (int)q.size(2),
-          (int)k.size(2), (int)D, (int)sh, q_seg.has_value()};
+          (int)k.size(2), (int)D, (int)sh, (int)lo, q_seg.has_value(), lower.has_value()};
 }
 
 // The one place that picks a general kernel's instantiation: head dim, and
-// the segment-masked variant when the call carries segment ids.
+// the segment-masked variant when the call carries segment ids, and the
+// windowed one when it carries a lower diagonal bound.
 #define FA_GEN_KERNEL(kernel, D) ((D) == 64 ? kernel<64> : kernel<128>)
+#define FA_GEN_KERNEL_WIN(kernel, s, SEG)                                   \
+  ((s).win ? ((s).D == 64 ? kernel<64, SEG, true> : kernel<128, SEG, true>) \
+           : ((s).D == 64 ? kernel<64, SEG, false> : kernel<128, SEG, false>))
 #define FA_GEN_KERNEL_SEG(kernel, s)                                        \
-  ((s).seg ? ((s).D == 64 ? kernel<64, true> : kernel<128, true>)           \
-           : ((s).D == 64 ? kernel<64, false> : kernel<128, false>))
+  ((s).seg ? FA_GEN_KERNEL_WIN(kernel, s, true) : FA_GEN_KERNEL_WIN(kernel, s, false))
 
 // Segment pre-pass: (min, max) id of every 64-row q and kv tile, the facts
 // the kernels skip tile pairs on.  Launched by both bindings (the backward
@@ -880,28 +887,32 @@ FaGenSeg fa_gen_seg(const Binding& b, const FaGenShape& s, const at::Tensor& lik
 
 std::vector<at::Tensor> fa_gen_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                    double scale, bool causal, int64_t shift,
-                                   OptTensor q_seg, OptTensor kv_seg) {
+                                   OptTensor q_seg, OptTensor kv_seg,
+                                   OptInt lower = {}) {
   // q: [B,Hq,Sq,D]; k,v: [B,Hkv,Sk,D] -> {o [B,Hq,Sq,D], lse [B,Hq,Sq] f32}
   // q_seg [B,Sq], kv_seg [B,Sk] int32 (both or neither): the segment mask
+  // lower (or none = no window): key j is visible to query i only if
+  // j >= i + lower
   Binding b("fa_gen_fwd", "q", q);
-  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift, q_seg, kv_seg);
+  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift, lower, q_seg, kv_seg);
   auto out = at::empty_like(q);
   auto lse = at::empty({s.B, s.Hq, s.Sq}, q.options().dtype(F32));
   FaGenSeg g = fa_gen_seg(b, s, q, q_seg, kv_seg);
   b.launch(FA_GEN_KERNEL_SEG(fa_gen_fwd_kernel, s),
            dim3((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B), FG_THREADS, bf16(q), bf16(k),
            bf16(v), bf16_mut(out), lse.data_ptr<float>(), s.Hq, s.Hkv, s.Sq, s.Sk,
-           (float)(scale * 1.4426950408889634), causal ? 1 : 0, s.shift, g.q, g.kv,
-           g.tiles);
+           (float)(scale * 1.4426950408889634), causal ? 1 : 0, s.shift, s.lower, g.q,
+           g.kv, g.tiles);
   return {out, lse};
 }
 
 std::vector<at::Tensor> fa_gen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                    at::Tensor o, at::Tensor dout, at::Tensor lse,
                                    OptTensor dlse, double scale, bool causal,
-                                   int64_t shift, OptTensor q_seg, OptTensor kv_seg) {
+                                   int64_t shift, OptTensor q_seg, OptTensor kv_seg,
+                                   OptInt lower = {}) {
   Binding b("fa_gen_bwd", "q", q);
-  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift, q_seg, kv_seg);
+  FaGenShape s = fa_gen_check(b, q, k, v, causal, shift, lower, q_seg, kv_seg);
   b.arg("o", o, BF16, q.sizes());
   b.arg("dout", dout, BF16, q.sizes());
   b.arg("lse", lse, F32, {s.B, s.Hq, s.Sq});
@@ -919,12 +930,12 @@ std::vector<at::Tensor> fa_gen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
            dim3((s.Sk + FG_BLK - 1) / FG_BLK, s.Hkv, s.B), FG_THREADS, bf16(q), bf16(k),
            bf16(v), bf16(dout), lse.data_ptr<float>(), delta.data_ptr<float>(),
            bf16_mut(dk), bf16_mut(dv), s.Hq, s.Hkv, s.Sq, s.Sk, (float)scale,
-           causal ? 1 : 0, s.shift, g.q, g.kv, g.tiles);
+           causal ? 1 : 0, s.shift, s.lower, g.q, g.kv, g.tiles);
   b.launch(FA_GEN_KERNEL_SEG(fa_gen_dq_kernel, s),
            dim3((s.Sq + FG_BLK - 1) / FG_BLK, s.Hq, s.B), FG_THREADS, bf16(q), bf16(k),
            bf16(v), bf16(dout), lse.data_ptr<float>(), delta.data_ptr<float>(),
            bf16_mut(dq), s.Hq, s.Hkv, s.Sq, s.Sk, (float)scale, causal ? 1 : 0,
-           s.shift, g.q, g.kv, g.tiles);
+           s.shift, s.lower, g.q, g.kv, g.tiles);
   return {dq, dk, dv};
 }
 
@@ -1044,13 +1055,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_gen_fwd", &fa_gen_fwd, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("causal"),
         pybind11::arg("shift"), pybind11::arg("q_seg") = pybind11::none(),
-        pybind11::arg("kv_seg") = pybind11::none());
+        pybind11::arg("kv_seg") = pybind11::none(),
+        pybind11::arg("lower") = pybind11::none());
   m.def("fa_gen_bwd", &fa_gen_bwd, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("dout"),
         pybind11::arg("lse"), pybind11::arg("dlse"), pybind11::arg("scale"),
         pybind11::arg("causal"), pybind11::arg("shift"),
         pybind11::arg("q_seg") = pybind11::none(),
-        pybind11::arg("kv_seg") = pybind11::none());
+        pybind11::arg("kv_seg") = pybind11::none(),
+        pybind11::arg("lower") = pybind11::none());
   m.def("permlane_probe", &permlane_probe);
   m.def("mfma32_probe", &mfma32_probe);
   m.def("tr_probe", &tr_probe);

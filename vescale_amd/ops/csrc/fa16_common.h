@@ -53,19 +53,36 @@ DEV int fg_kv_tiles(int q0, int Sq, int Sk, int causal, int shift) {
   return kv_end > 0 ? (kv_end + FG_BLK - 1) / FG_BLK : 0;
 }
 
+// Window (band mask), the lower diagonal bound col >= row + lower.  Both
+// tile bounds below are block-uniform scalars; the end of the kv range stays
+// fg_kv_tiles and the start of the q range the causal one.
+// First KV tile a q tile starting at q0 has to visit: its rows see no key
+// before column q0 + lower.  At or past fg_kv_tiles: an empty range, dead rows.
+DEV int fg_kv_first(int q0, int lower) { return max(0, q0 + lower) / FG_BLK; }
+
+// Number of leading q tiles a kv tile starting at k0 has to visit: its last
+// key, min(k0 + 63, Sk - 1), is seen by no row past itself - lower.  0 if that
+// row is negative.
+DEV int fg_q_tiles(int k0, int Sq, int Sk, int lower) {
+  int row = min(Sq - 1, min(k0 + FG_BLK - 1, Sk - 1) - lower);
+  return row >= 0 ? row / FG_BLK + 1 : 0;
+}
+
 // key `col` is visible to query `row`
 DEV bool fg_vis(int row, int col, int Sk, int causal, int shift) {
   return col < Sk && (!causal || col <= row + shift);
 }
 
-// Segment (document) mask, a compile-time variant of the family: with SEG,
-// key `col` is visible to query `row` iff the rule above holds AND the two
-// rows carry the same segment id.  Ids are compared for equality only; no
-// value is special and they need not be sorted.  Without SEG the ids are
-// dead arguments and the test is the one above.
-template <bool SEG>
-DEV bool fg_vis(int row, int col, int Sk, int causal, int shift, int qs, int ks) {
+// Segment (document) mask and window, the compile-time variants of the
+// family.  With SEG, key `col` is visible to query `row` iff the rule above
+// holds AND the two rows carry the same segment id.  Ids are compared for
+// equality only; no value is special and they need not be sorted.  With WIN,
+// iff in addition col >= row + lower.  Without SEG the ids, without WIN
+// `lower`, are dead arguments; with neither the test is the one above.
+template <bool SEG, bool WIN>
+DEV bool fg_vis(int row, int col, int Sk, int causal, int shift, int lower, int qs, int ks) {
   bool vis = fg_vis(row, col, Sk, causal, shift);
+  if constexpr (WIN) vis = vis && col >= row + lower;
   if constexpr (SEG) vis = vis && qs == ks;
   return vis;
 }

@@ -633,23 +633,26 @@ def flash_attention_causal(q, k, v):
 # optional causal mask  j <= i + causal_shift.
 # ---------------------------------------------------------------------------
 def _attention_ref(q, k, v, is_causal, shift, scale, dtype=None, *, q_seg=None,
-                   kv_seg=None):
+                   kv_seg=None, lower=None):
     """Differentiable torch attention returning (out, lse): the CPU path and
     the oracle of the general kernel.  Matmuls and softmax run in `dtype`
     (default: fp32, or q's dtype if wider); GQA by head grouping; key j is
     visible to query i iff j <= i + shift and, with q_seg [B,Sq] / kv_seg
-    [B,Sk] given, kv_seg[b, j] == q_seg[b, i]; a row with no visible key
-    gives out = 0, lse = -inf and zero gradients."""
+    [B,Sk] given, kv_seg[b, j] == q_seg[b, i] and, with `lower` given,
+    j >= i + lower; a row with no visible key gives out = 0, lse = -inf and
+    zero gradients."""
     if dtype is None:
         dtype = torch.promote_types(q.dtype, torch.float32)
     B, Hq, Sq, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
     qg = q.to(dtype).reshape(B, Hkv, Hq // Hkv, Sq, D)
     s = (qg @ k.to(dtype).unsqueeze(2).transpose(-1, -2)) * scale
+    i = torch.arange(Sq, device=q.device).unsqueeze(1)
+    j = torch.arange(Sk, device=q.device).unsqueeze(0)
     if is_causal:
-        i = torch.arange(Sq, device=q.device).unsqueeze(1)
-        j = torch.arange(Sk, device=q.device).unsqueeze(0)
         s = s.masked_fill(j > i + shift, float("-inf"))
+    if lower is not None:
+        s = s.masked_fill(j < i + lower, float("-inf"))
     if q_seg is not None:
         other = q_seg.unsqueeze(2) != kv_seg.unsqueeze(1)       # [B, Sq, Sk]
         s = s.masked_fill(other[:, None, None], float("-inf"))
@@ -670,14 +673,16 @@ class _FlashAttentionGen(torch.autograd.Function):
     """fa_gen_fwd / fa_gen_bwd: one node with two differentiable outputs.
     q_seg / kv_seg (contiguous int32 [B,Sq] / [B,Sk], or both None) are
     non-differentiable inputs; backward hands the ids themselves to
-    fa_gen_bwd, which derives its tile bounds again."""
+    fa_gen_bwd, which derives its tile bounds again.  lower (int or None):
+    the window's bound j >= i + lower, the WIN kernels."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal, shift, q_seg=None, kv_seg=None):
+    def forward(ctx, q, k, v, scale, causal, shift, q_seg=None, kv_seg=None,
+                lower=None):
         out, lse = _ext().fa_gen_fwd(q, k, v, scale, causal, shift,
-                                     q_seg=q_seg, kv_seg=kv_seg)
+                                     q_seg=q_seg, kv_seg=kv_seg, lower=lower)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.args = (scale, causal, shift)
+        ctx.args = (scale, causal, shift, lower)
         ctx.seg = (q_seg, kv_seg)
         ctx.set_materialize_grads(False)
         return out, lse
@@ -685,16 +690,16 @@ class _FlashAttentionGen(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, dlse):
         q, k, v, out, lse = ctx.saved_tensors
-        scale, causal, shift = ctx.args
+        scale, causal, shift, lower = ctx.args
         q_seg, kv_seg = ctx.seg
         dout = torch.zeros_like(out) if dout is None else dout.contiguous()
         if dlse is not None:
             dlse = dlse.float().contiguous()
         dq, dk, dv = _ext().fa_gen_bwd(
             q, k, v, out, dout, lse, dlse, scale, causal, shift,
-            q_seg=q_seg, kv_seg=kv_seg
+            q_seg=q_seg, kv_seg=kv_seg, lower=lower
         )
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def _segment_args(q_segment_ids, kv_segment_ids, B, Sq, Sk):
@@ -718,6 +723,29 @@ def _segment_args(q_segment_ids, kv_segment_ids, B, Sq, Sk):
             raise ValueError(f"{name} must be [B, S] = [{B}, {S}], got {list(t.shape)}")
         out.append(t.to(torch.int32).contiguous())
     return out[0], out[1]
+
+
+def _window_args(window, is_causal, causal_shift):
+    """flash_attention's window rules: the kernels' (causal, shift, lower)
+    for window = (left, right) around the diagonal d(i) = i + causal_shift.
+    An upper bound is what (causal, shift) already express, so `right` is
+    folded into them; only lower = causal_shift - left is new."""
+    if not isinstance(window, (tuple, list)) or len(window) != 2:
+        raise ValueError(f"window must be a pair (left, right), got {window!r}")
+    for side, w in zip(("left", "right"), window):
+        if w is None:
+            continue
+        if isinstance(w, bool) or not isinstance(w, int):
+            raise ValueError(f"window {side} must be an int or None, got {w!r}")
+        if w < 0:
+            raise ValueError(f"window {side} must be >= 0, got {w}")
+    left, right = window
+    lower = None if left is None else causal_shift - left
+    if is_causal:
+        return True, causal_shift, lower     # j <= d(i) already implies right
+    if right is None:
+        return False, 0, lower
+    return True, causal_shift + right, lower
 
 
 def segment_ids_from_cu_seqlens(cu_seqlens, total: int) -> torch.Tensor:
@@ -754,7 +782,7 @@ def _run_start_ids(ids):
 
 def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
                     return_lse=False, q_segment_ids=None, kv_segment_ids=None,
-                    contiguous_segments=False):
+                    contiguous_segments=False, window=None):
     """Attention over q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (Hq % Hkv == 0).
 
     With is_causal, key j is visible to query i iff j <= i + causal_shift
@@ -762,6 +790,18 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
     with no visible key yields out = 0, lse = -inf and zero gradients.
     Returns out, or (out, lse) with lse [B,Hq,Sq] fp32 (natural log) when
     return_lse; both outputs are differentiable.
+
+    Sliding window (local attention): window = (left, right), each a
+    non-negative int or None (unbounded on that side), around the diagonal
+    d(i) = i + causal_shift: key j is visible to query i iff, in addition to
+    every other rule, j >= d(i) - left and j <= d(i) + right.  With is_causal,
+    right adds nothing; is_causal=True with window=(W - 1, 0) is the
+    sliding_window = W of Mistral-style models.  causal_shift is allowed
+    without is_causal when a window is given (Sk - Sq: a bottom-right aligned
+    band).  A row the window leaves with no key is a dead row as above.  Bad
+    windows (negative or non-int entries, not a pair) raise ValueError.  The
+    general kernels skip the key tiles left of the band and the query tiles
+    below it, so the work is O(S * W), not O(S^2).
 
     Packed sequences: with q_segment_ids [B,Sq] and kv_segment_ids [B,Sk]
     (any integer dtype) key j is visible to query i iff, in addition,
@@ -787,13 +827,18 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
 
     Dispatch: (1) the tuned D=128 causal kernels when their gate holds, no
     lse is wanted and there are no segment ids, or the ids come with
-    contiguous_segments; (2) the general HIP kernel
+    contiguous_segments, and there is no window (the tuned kernels have no
+    band mask: a call with a window never takes them); (2) the general HIP kernel
     for bf16 on GPU with D in {64, 128}; (3) the torch reference (CPU, other
     dtypes / head dims, VESCALE_FA=aten)."""
     import math
 
-    if causal_shift != 0 and not is_causal:
+    if window is not None:
+        causal, shift, lower = _window_args(window, bool(is_causal), int(causal_shift))
+    elif causal_shift != 0 and not is_causal:
         raise ValueError("causal_shift != 0 requires is_causal=True")
+    else:
+        causal, shift, lower = bool(is_causal), int(causal_shift), None
     B, Hq, Sq, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
     if contiguous_segments:
@@ -816,7 +861,7 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
         and Hq % Hkv == 0
         and _use_hip(q, k, v)
     )
-    if (hip and not return_lse and is_causal and causal_shift == 0
+    if (hip and not return_lse and window is None and is_causal and causal_shift == 0
             and Sq == Sk and D == 128 and Sq % 256 == 0
             and (q_seg is None or (contiguous_segments and
                                    os.environ.get("VESCALE_FA_SEG", "tuned") != "gen"))):
@@ -828,12 +873,11 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
     if hip:
         out, lse = _FlashAttentionGen.apply(
             q.contiguous(), k.contiguous(), v.contiguous(), float(scale),
-            bool(is_causal), int(causal_shift),
-            q_seg, kv_seg,
+            causal, shift, q_seg, kv_seg, lower,
         )
     else:
-        out, lse = _attention_ref(q, k, v, is_causal, causal_shift, scale,
-                                  q_seg=q_seg, kv_seg=kv_seg)
+        out, lse = _attention_ref(q, k, v, causal, shift, scale,
+                                  q_seg=q_seg, kv_seg=kv_seg, lower=lower)
     return (out, lse) if return_lse else out
 
 
