@@ -22,10 +22,16 @@ graph, so the reverse-order backward sendrecvs pair up deadlock-free.
 Memory note: the default impl="eager" reference keeps per-step
 O(S_local^2) score activations alive for autograd and circulates GQA keys
 and values expanded to Hq heads.  impl="flash" runs every block through
-ops.flash_attention (the general-shape HIP kernel on GPU, its torch
-reference elsewhere), which returns (out, lse) and recomputes scores in
-backward: saved state per ring step is O(S_local * D) — q, the KV block,
-out and lse — and k/v travel the ring with their own Hkv heads.
+ops.flash_attention (HIP kernels on GPU, its torch reference elsewhere),
+which returns (out, lse) and recomputes scores in backward: saved state per
+ring step is O(S_local * D) — q, the KV block, out and lse — and k/v travel
+the ring with their own Hkv heads.  Which kernels run a block (bf16, D = 128,
+S_local % 256 == 0, no segment ids): the diagonal block (causal, shift 0)
+the tuned 32x32 causal kernels with the lse handed out, a past block (no
+mask) their FULL instantiations; a future block (negative shift, wholly
+masked) stays on the general kernel, which skips all its tiles.  Any other
+shape, D = 64 or segment ids: every block on the general kernels
+(VESCALE_FA_FULL=gen forces that).
 
 Causality is exact across blocks: with q-block index i and kv-block
 index j (global offsets i*S_local, j*S_local), j>i contributes nothing
@@ -151,7 +157,9 @@ def ring_sdpa(
     the query-head grouping like F.scaled_dot_product_attention with
     enable_gqa.  impl="flash" computes each block with ops.flash_attention
     (see the module docstring's memory note); it needs the default
-    [B, H, S, D] layout (seq_dim == 2).
+    [B, H, S, D] layout (seq_dim == 2).  With bf16, D = 128, S_local % 256
+    == 0 and no segment_ids its diagonal and past blocks run on the tuned
+    32x32 kernels (causal with lse / FULL), future blocks on the general one.
 
     segment_ids: this rank's local [B, S_local] slice (a plain integer
     tensor) of the packed rows' [B, S] segment ids; a token attends only to

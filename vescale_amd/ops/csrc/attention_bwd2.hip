@@ -37,6 +37,12 @@
 // with ff_mask on boundary tiles only.  The kernels without the suffix are the
 // SEG=false instantiations; the fused fa2_dvdk has no SEG form.
 //
+// No mask (fa2_dq_full / fa2_dv_full / fa2_dk_full, template FULL): Sq rows of
+// q, dout, lse, delta and dq against Sk rows of k, v and the dk / dv partials.
+// dq (grid Sq/256) walks every kv tile, dv and dk (grid Sk/256) every q tile;
+// the GQA reduction runs over Sk rows.  fa_bwd_preprocess_dlse folds a
+// cotangent of the logsumexp into delta, for every form of the kernels.
+//
 // Reference parity: the reference framework uses the stock flash kernels;
 // this replaces the train step's heaviest kernel (the library backward is
 // 30% of the Llama-8B step — profiles/bench_kernel_stats_r1_final.txt).
@@ -52,10 +58,16 @@
 // ---------------------------------------------------------------------------
 // delta = rowsum(dO * O)   [B*H*S rows of D elems]
 // ---------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(256)
-fa_bwd_preprocess(const unsigned short* __restrict__ dout,
-                  const unsigned short* __restrict__ o,
-                  float* __restrict__ delta, int64_t rows, int Hq, int S, int bshd) {
+// DLSE: the output also has a cotangent, dlse [B,Hq,S] fp32 on the logsumexp.
+// d lse_i / d s_ij = P_ij, so dS = P * (dP - delta) + P * dlse = P * (dP -
+// (delta - dlse)) and dV is untouched: the pass writes delta - dlse and the dq /
+// dk kernels run as they are.  dlse is indexed like delta (null and never read
+// when !DLSE).
+template <bool DLSE>
+DEV void fa_bwd_preprocess_t(const unsigned short* __restrict__ dout,
+                             const unsigned short* __restrict__ o,
+                             const float* __restrict__ dlse,
+                             float* __restrict__ delta, int64_t rows, int Hq, int S, int bshd) {
   // 16 lanes per row (8 elems each), 16 rows per 256-thread block per
   // iteration; fully coalesced loads, shfl-xor reduce inside each 16-lane
   // group, no barriers — HBM-roofline for this pure-bandwidth pass.
@@ -83,8 +95,25 @@ fa_bwd_preprocess(const unsigned short* __restrict__ dout,
       const unsigned bi = bs / (unsigned)S, sq = bs - bi * (unsigned)S;
       drow = ((int64_t)bi * Hq + h) * S + sq;
     }
-    if (sub == 0) delta[drow] = s;
+    if constexpr (DLSE) {
+      if (sub == 0) delta[drow] = s - dlse[drow];
+    } else {
+      if (sub == 0) delta[drow] = s;
+    }
   }
+}
+extern "C" __global__ void __launch_bounds__(256)
+fa_bwd_preprocess(const unsigned short* __restrict__ dout,
+                  const unsigned short* __restrict__ o,
+                  float* __restrict__ delta, int64_t rows, int Hq, int S, int bshd) {
+  fa_bwd_preprocess_t<false>(dout, o, nullptr, delta, rows, Hq, S, bshd);
+}
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(256)
+fa_bwd_preprocess_dlse(const unsigned short* __restrict__ dout,
+                       const unsigned short* __restrict__ o,
+                       const float* __restrict__ dlse,
+                       float* __restrict__ delta, int64_t rows, int Hq, int S, int bshd) {
+  fa_bwd_preprocess_t<true>(dout, o, dlse, delta, rows, Hq, S, bshd);
 }
 
 // ---------------------------------------------------------------------------
@@ -129,7 +158,10 @@ fa_bwd_reduce_gqa(const unsigned short* __restrict__ part,  // [B,Hq,S,D]
 // over unchanged: a masked score is -inf before the fma, P = exp2(-inf - lse2)
 // = +0 and dS = 0 * (dP - delta) = 0, whether one element of a lane's tile is
 // masked or all of them.
-template <bool SEG>
+// FULL: no mask, S rows of q / dout / lse / delta / dq and Sk rows of k / v (Sk
+// is read in FULL only); every block walks all Sk/64 kv tiles and every wave is
+// active in each, so `active`, `need_mask` and ff_mask are compiled out.
+template <bool SEG, bool FULL = false>
 DEV void fa2_dq_t(const unsigned short* __restrict__ q,
             const unsigned short* __restrict__ k,
             const unsigned short* __restrict__ v,
@@ -138,14 +170,15 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
             const float* __restrict__ delta,
             unsigned short* __restrict__ dq,
             int B, int Hq, int Hkv, int S, float scale, int bshd,
-            const int* __restrict__ bounds) {
+            const int* __restrict__ bounds, int Sk = 0) {
+  static_assert(!(SEG && FULL), "FULL has no mask at all");
   // 2 x 16 + 2 x 16 + 64 = 128 KiB of the CU's 160: one block per CU, as the
   // 256 VGPRs of its 8 waves decide anyway
   __shared__ unsigned short lk[2][FB_OTH * FB_D];  // K kv-tile (swz), double-buffered
   __shared__ unsigned short lv[2][FB_OTH * FB_D];  // V kv-tile (swz), double-buffered
   __shared__ unsigned short ldo[FB_TILE * FB_D];   // block's dO q rows (swz)
 
-  const ff_ctx c = ff_prologue(Hq, Hkv, S);
+  const ff_ctx c = ff_prologue(Hq, Hkv, S, FULL ? Sk : S);
   const int tid = c.tid, l31 = c.l31, half = c.half;
   // The wave index in a scalar register: `active` and `need_mask` below are
   // then scalar compares and branches, and the epilogue rebuilds its row from
@@ -156,7 +189,14 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
   // blocks that start last are the cheap ones and the kernel's tail is short
   // (4.66 -> 4.50 ms per call at the bench shape).  Blocks do not
   // communicate: results are bitwise those of the ascending order.
-  const int qt = (int)gridDim.x - 1 - c.tile;
+  // FULL: every tile costs the same Sk/64 kv tiles, so there is no heavy end to
+  // start first and the order within a head is left ascending.  What matters
+  // there is which blocks run at the same time: the Sq/256 q tiles of the
+  // Hq/Hkv heads of one (batch, kv head) stream the same K/V, they are
+  // consecutive in the flat grid (tile fastest, then head), and ff_xcd_remap
+  // gives each XCD a contiguous piece of it, so they meet in one L2.  The remap
+  // is kept for that reason; the reversal has none here.
+  const int qt = FULL ? c.tile : (int)gridDim.x - 1 - c.tile;
   const int64_t qbase = c.qbase, kbase = c.kbase;
   const int q0 = qt * FB_TILE + wave * FB_OWN;
   const int my_q = q0 + l31;
@@ -181,7 +221,7 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
 #pragma unroll
   for (int i = 0; i < 4; ++i) dqacc[i] = (ff_floatx16)(0.f);
 
-  const int last_kv = min((qt + 1) * (FB_TILE / FB_OTH), S / FB_OTH);
+  const int last_kv = FULL ? Sk / FB_OTH : min((qt + 1) * (FB_TILE / FB_OTH), S / FB_OTH);
   const unsigned short* kg = k + kbase;
   const unsigned short* vg = v + kbase;
 
@@ -211,8 +251,10 @@ DEV void fa2_dq_t(const unsigned short* __restrict__ q,
   for (int jkv = first_kv; jkv < last_kv; ++jkv) {
     const int kv0 = jkv * FB_OTH;
     const int buf = jkv & 1;
-    bool active = (kv0 <= q0 + FB_OWN - 1);
-    const bool need_mask = (kv0 + FB_OTH - 1 > q0);
+    // FULL: both are compile-time constants.  lse is finite there as well
+    // (the log of a sum over Sk >= 64 keys), so P = exp2(x - lse2) needs no guard.
+    bool active = FULL || (kv0 <= q0 + FB_OWN - 1);
+    const bool need_mask = !FULL && (kv0 + FB_OTH - 1 > q0);
     // SEG: inactive while the tile lies before the wave's first document; the
     // second bound is applied on the tiles that begin before its last one
     bool need_seg = false;
@@ -328,6 +370,24 @@ fa2_dq_seg_bf16(const unsigned short* __restrict__ q,
                 int B, int Hq, int Hkv, int S, float scale, int bshd) {
   fa2_dq_t<true>(q, k, v, dout, lse, delta, dq, B, Hq, Hkv, S, scale, bshd, bounds);
 }
+// Resources of the FULL instantiations (the same flags and remarks), each at 2
+// waves/SIMD with scratch 0 and no spills:
+//   fa2_dq_full_bf16  252 VGPRs, 0 AGPRs, 128 KiB LDS
+//   fa2_dv_full_bf16  182 VGPRs, 0 AGPRs, 66048 B LDS
+//   fa2_dk_full_bf16  250 VGPRs, 0 AGPRs, 66560 B LDS
+// (fa_bwd_preprocess_dlse: 28 VGPRs, no LDS, 8 waves/SIMD)
+// fa2_dq without a mask; grid (Sq/256, Hq, B)
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
+fa2_dq_full_bf16(const unsigned short* __restrict__ q,
+                 const unsigned short* __restrict__ k,
+                 const unsigned short* __restrict__ v,
+                 const unsigned short* __restrict__ dout,
+                 const float* __restrict__ lse,
+                 const float* __restrict__ delta,
+                 unsigned short* __restrict__ dq,
+                 int B, int Hq, int Hkv, int Sq, int Sk, float scale, int bshd) {
+  fa2_dq_t<false, true>(q, k, v, dout, lse, delta, dq, B, Hq, Hkv, Sq, scale, bshd, nullptr, Sk);
+}
 
 // ---------------------------------------------------------------------------
 // fa2_dv / fa2_dk: one body, two instantiations; grid (S/256 kv-tiles, Hq, B),
@@ -339,7 +399,11 @@ fa2_dq_seg_bf16(const unsigned short* __restrict__ q,
 // SEG: dv and dk own kv rows, so a lane keeps my_end = end[b][my_kv] and the
 // mask is kv <= q < my_end; the q-tile loop ends at the block's last row's
 // document end (the block's maximum), not at S.
-template <bool DK, bool SEG>
+// FULL: no mask; the block owns 256 of the Sk kv rows (grid.x = Sk/256) and
+// walks all S/64 q tiles from tile 0, every wave active in each.  S stays the
+// length of q / dout / lse / delta; k, v and out_part [B,Hq,Sk,D] have Sk rows
+// (read in FULL only).
+template <bool DK, bool SEG, bool FULL = false>
 DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
                      const unsigned short* __restrict__ k,
                      const unsigned short* __restrict__ v,
@@ -348,16 +412,20 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
                      const float* __restrict__ delta,
                      unsigned short* __restrict__ out_part,
                      int Hq, int Hkv, int S, float scale, int bshd,
-                     const int* __restrict__ bounds) {
+                     const int* __restrict__ bounds, int Sk = 0) {
+  static_assert(!(SEG && FULL), "FULL has no mask at all");
   // every q-tile array double-buffered (buffer = tile index & 1): about 66 KiB
   __shared__ unsigned short lq[2][FB_OTH * FB_D];   // Q q-tile (swz)
   __shared__ unsigned short ldo[2][FB_OTH * FB_D];  // dO q-tile (swz)
   __shared__ float llse[2][FB_OTH];                 // q-tile rows' lse2
   __shared__ float ldelta[2][FB_OTH];               // dk only: never referenced, so never allocated, in dv
 
-  const ff_ctx c = ff_prologue(Hq, Hkv, S);
+  const ff_ctx c = ff_prologue(Hq, Hkv, S, FULL ? Sk : S);
   const int tid = c.tid, wave = c.wave, l31 = c.l31, half = c.half;
   const int64_t qbase = c.qbase, kbase = c.kbase;
+  // this head's rows of the per-Hq partial: q-shaped in the square kernels,
+  // Sk rows per head in FULL
+  const int64_t pbase = FULL ? (((int64_t)c.b * Hq + c.h) * Sk) * FB_D : qbase;
   const int kvB = c.tile * FB_TILE;
   const int kv0w = kvB + wave * FB_OWN;
   const int my_kv = kv0w + l31;
@@ -380,7 +448,7 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
 #pragma unroll
   for (int i = 0; i < 4; ++i) acc[i] = (ff_floatx16)(0.f);
 
-  const int jq0 = kvB / FB_OTH;       // diagonal q tile, block-uniform
+  const int jq0 = FULL ? 0 : kvB / FB_OTH;  // diagonal q tile (FULL: the first), block-uniform
   int n_jq = S / FB_OTH;
   // SEG: end is monotone, so the wave's first row (lane 0) holds its smallest
   // end, its last row (lane 31) the largest, and the block's last row the
@@ -421,8 +489,9 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
     const int qt0 = jq * FB_OTH;
     const int buf = jq & 1;
     const bool have_next = (jq + 1 < n_jq);  // block-uniform
-    bool active = (qt0 + FB_OTH - 1 >= kv0w);
-    const bool need_mask = (qt0 < kv0w + FB_OWN - 1);
+    // FULL: compile-time constants, as in fa2_dq
+    bool active = FULL || (qt0 + FB_OTH - 1 >= kv0w);
+    const bool need_mask = !FULL && (qt0 < kv0w + FB_OWN - 1);
     // SEG: inactive once the tile lies past the wave's last document; the
     // second bound is applied on the tiles that reach the end of its first
     bool need_seg = false;
@@ -529,8 +598,32 @@ DEV void fa2_dv_dk_t(const unsigned short* __restrict__ q,
   ff_stage_wait();  // no tile at all: nothing may be pending when the wave ends
 
   // epilogue (rows = d over regs, col = kv = l31 -> row write); dK = scale * acc
-  unsigned short* og = out_part + qbase + (int64_t)my_kv * FB_D;
+  unsigned short* og = out_part + pbase + (int64_t)my_kv * FB_D;
   ff_store_row<DK>(og, acc, scale, half);
+}
+
+// fa2_dv / fa2_dk without a mask; grid (Sk/256, Hq, B), partials [B,Hq,Sk,D]
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
+fa2_dv_full_bf16(const unsigned short* __restrict__ q,
+                 const unsigned short* __restrict__ k,
+                 const unsigned short* __restrict__ dout,
+                 const float* __restrict__ lse,
+                 unsigned short* __restrict__ dv_part,
+                 int B, int Hq, int Hkv, int Sq, int Sk, float scale, int bshd) {
+  fa2_dv_dk_t<false, false, true>(q, k, nullptr, dout, lse, nullptr, dv_part, Hq, Hkv, Sq, scale,
+                                  bshd, nullptr, Sk);
+}
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)
+fa2_dk_full_bf16(const unsigned short* __restrict__ q,
+                 const unsigned short* __restrict__ k,
+                 const unsigned short* __restrict__ v,
+                 const unsigned short* __restrict__ dout,
+                 const float* __restrict__ lse,
+                 const float* __restrict__ delta,
+                 unsigned short* __restrict__ dk_part,
+                 int B, int Hq, int Hkv, int Sq, int Sk, float scale, int bshd) {
+  fa2_dv_dk_t<true, false, true>(q, k, v, dout, lse, delta, dk_part, Hq, Hkv, Sq, scale, bshd,
+                                 nullptr, Sk);
 }
 
 extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FB_THREADS, 2)

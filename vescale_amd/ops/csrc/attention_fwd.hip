@@ -40,6 +40,11 @@
 //     starts at its first row's document (the prologue stages THAT tile) and
 //     a wave computes and masks by two scalars.  fa_fwd_bf16 is the SEG=false
 //     instantiation: the instructions it had before the template.
+//   - no mask (fa_fwd_full_bf16, template FULL): every q row sees every key,
+//     and q and k/v have lengths of their own (Sq rows of q, o and lse, Sk rows
+//     of k and v): encoders, cross attention, the past blocks of ring
+//     attention.  Every block walks all Sk/64 kv tiles and no wave is ever
+//     inactive, so the activity test, the mask and its compare are compiled out.
 // Capability parity: reference vescale relies on library flash attention;
 // this is the MI355X-native forward for the train step's hot op.
 #include "fa32_common.h"
@@ -52,18 +57,21 @@
 
 // SEG: the packed-document mask of fa32_common.h (bounds [B,2,S] from the
 // pre-pass; null and never read when !SEG).
-template <int MODE, bool SEG = false>  // 0=full, 1=no-softmax, 2=no-PV, 3=no-ST, 4=no-gating, 5=exp-domain (bisect)
+// FULL: no mask, S rows of q / o / lse and Sk rows of k / v (Sk is read in
+// FULL only: the masked kernels are square).  Never combined with SEG.
+template <int MODE, bool SEG = false, bool FULL = false>  // MODE: 0=whole kernel, 1=no-softmax, 2=no-PV, 3=no-ST, 4=no-gating, 5=exp-domain (bisect)
 DEV void fa_fwd_t(const unsigned short* __restrict__ q,
             const unsigned short* __restrict__ k,
             const unsigned short* __restrict__ v,
             unsigned short* __restrict__ out,
             float* __restrict__ lse,
             int B, int Hq, int Hkv, int S, float scale, int out_bshd,
-            const int* __restrict__ bounds = nullptr) {
+            const int* __restrict__ bounds = nullptr, int Sk = 0) {
+  static_assert(!(SEG && FULL), "FULL has no mask at all");
   __shared__ unsigned short lk[2][FF_KV * FF_D];  // K, swizzled
   __shared__ unsigned short lv[2][FF_KV * FF_D];  // V, swizzled (same as K)
 
-  const ff_ctx c = ff_prologue(Hq, Hkv, S);
+  const ff_ctx c = ff_prologue(Hq, Hkv, S, FULL ? Sk : S);
   const int tid = c.tid, lane = c.lane, l31 = c.l31, half = c.half;
   // q macro-tile, ascending.  (Walking a head's tiles heaviest first, as
   // fa2_dq does, was measured here too: 3.51 -> 3.42 ms per call, inside this
@@ -89,8 +97,9 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
 
   // BLOCK-UNIFORM kv loop bound (all 4 waves hit the same barriers):
   // cover kv < (qt+1)*128, i.e. through the block's last causal tile.
+  // FULL: every tile of k, the same for all blocks.
   const int n_kv = (qt + 1) * (FF_QTILE / FF_KV);
-  const int last_kv = min(n_kv, S / FF_KV);
+  const int last_kv = FULL ? Sk / FF_KV : min(n_kv, S / FF_KV);
 
   // SEG: one integer per lane, the first key of its row's document; the mask
   // is my_start <= kv <= my_q.  start is monotone, so the wave's first row
@@ -136,9 +145,15 @@ DEV void fa_fwd_t(const unsigned short* __restrict__ q,
     // lanes whose whole tile is masked (their document begins after it): the
     // dead-lane guard below is theirs.  Tiles inside one document stay on the
     // unmasked path.
-    bool active = (MODE == 4) || (kv0 <= q0 + FF_QBLK - 1);
+    // FULL: every wave is active in every tile and nothing is masked: both
+    // flags are compile-time constants, the branch on `active` and the masked
+    // arm below are not compiled.  No guard is needed either: every lane sees
+    // 64 keys in its first tile (Sk >= 64), so m_new and from then on m_run
+    // are finite, the first corr is exp2(-inf - finite) = 0 and no
+    // exp2(-inf - -inf) is ever evaluated.
+    bool active = FULL || (MODE == 4) || (kv0 <= q0 + FF_QBLK - 1);
     // wave-uniform mask need: only diagonal tiles pay the per-element cmp
-    bool need_mask = (MODE == 4) || (kv0 + FF_KV - 1 > q0);
+    bool need_mask = !FULL && ((MODE == 4) || (kv0 + FF_KV - 1 > q0));
     if constexpr (SEG) {
       active = active && (kv0 + FF_KV - 1 >= wstart_lo);
       need_mask = need_mask || (kv0 < wstart_hi);
@@ -330,6 +345,16 @@ fa_fwd_bf16_ab5(const unsigned short* q, const unsigned short* k,
 extern "C" __global__ void __launch_bounds__(FF_SEG_THREADS)
 fa_seg_bounds_i32(const int* ids, int* bounds, int S) {
   ff_seg_bounds(ids, bounds, S);
+}
+// fa_fwd_bf16 without a mask, Sq rows of q against Sk rows of k / v; grid
+// (Sq/128, Hq, B).  Resources (the extension's flags,
+// -Rpass-analysis=kernel-resource-usage): 199 VGPRs, 0 AGPRs, 64 KiB LDS,
+// scratch 0, no spills, 2 waves/SIMD.
+extern "C" __global__ void FF_NO_PK_F32 __launch_bounds__(FF_THREADS, 2)
+fa_fwd_full_bf16(const unsigned short* q, const unsigned short* k,
+                 const unsigned short* v, unsigned short* out, float* lse,
+                 int B, int Hq, int Hkv, int Sq, int Sk, float scale, int out_bshd) {
+  fa_fwd_t<0, false, true>(q, k, v, out, lse, B, Hq, Hkv, Sq, scale, out_bshd, nullptr, Sk);
 }
 // fa_fwd_bf16 with the packed-document mask.  Resources (the extension's flags,
 // -Rpass-analysis=kernel-resource-usage): 204 VGPRs, 0 AGPRs, 64 KiB LDS,

@@ -662,33 +662,41 @@ at::Tensor gemm_tn8(at::Tensor a, Weights bw, int64_t mode, OptTensor group_offs
   return c;
 }
 
-// ------------------------------ tuned flash attention (causal, D=128) ------
-struct FaShape { int B, Hq, Hkv, S; };
+// ------------------------------ tuned flash attention (D=128) --------------
+struct FaShape { int B, Hq, Hkv, S, Sk; };  // S: rows of q; Sk: rows of k and v
 
-// q: [B,Hq,S,128]; k,v: [B,Hkv,S,128]; lse: [B,Hq,S] f32; S % tile == 0.
+// q: [B,Hq,S,128]; k,v: [B,Hkv,Sk,128]; lse: [B,Hq,S] f32.  causal: Sk == S
+// and S % tile == 0.  !causal (the FULL kernels): Sk is k's own length, and
+// both are positive multiples of 256 within the same int ranges.
 // o,dout: [B,Hq,S,128], or with bshd [B,S,Hq,128].  The forward bindings pass
 // no o/dout/lse.
 FaShape fa_check(const Binding& b, int tile, const at::Tensor& q, const at::Tensor& k,
                  const at::Tensor& v, const OptTensor& o = {},
-                 const OptTensor& dout = {}, const OptTensor& lse = {}, bool bshd = false) {
+                 const OptTensor& dout = {}, const OptTensor& lse = {}, bool bshd = false,
+                 bool causal = true) {
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4, b.fn, ": q, k must be [B,H,S,128], got q sizes=",
               q.sizes(), " k sizes=", k.sizes());
   int64_t B = q.size(0), Hq = q.size(1), S = q.size(2), Hkv = k.size(1);
+  const int64_t Sk = causal ? S : k.size(2);
+  if (!causal) tile = FB_TILE;
   TORCH_CHECK(S >= 1 && S % tile == 0 && S <= INT_MAX, b.fn, ": seq = ", S,
               " must be a positive multiple of ", tile);
+  TORCH_CHECK(Sk >= 1 && Sk % tile == 0 && Sk <= INT_MAX, b.fn, ": with causal=False the ",
+              "k/v seq = ", Sk, " must be a positive multiple of ", tile);
   TORCH_CHECK(B >= 1 && Hkv >= 1 && Hq >= 1 && Hq % Hkv == 0, b.fn, ": B = ", B,
               " must be >= 1 and Hq = ", Hq, " a positive multiple of Hkv = ", Hkv);
   b.arg("q", q, BF16, {B, Hq, S, FF_D});
-  b.arg("k", k, BF16, {B, Hkv, S, FF_D});
-  b.arg("v", v, BF16, {B, Hkv, S, FF_D});
+  b.arg("k", k, BF16, {B, Hkv, Sk, FF_D});
+  b.arg("v", v, BF16, {B, Hkv, Sk, FF_D});
   // the [B,S,Hq,D] kernels index rows and a 256-row tile's elements in int
-  TORCH_CHECK(!bshd || (B * Hq * S <= INT_MAX && Hq * FF_D * 256 <= INT_MAX), b.fn,
-              ": B * Hq * S and Hq * 32768 must fit int in the [B,S,Hq,D] layout");
+  TORCH_CHECK(!bshd || (B * Hq * S <= INT_MAX && B * Hq * Sk <= INT_MAX &&
+                        Hq * FF_D * 256 <= INT_MAX),
+              b.fn, ": B * Hq * S and Hq * 32768 must fit int in the [B,S,Hq,D] layout");
   const Shape oshape = bshd ? Shape{B, S, Hq, FF_D} : Shape{B, Hq, S, FF_D};
   b.arg("o", o, BF16, oshape);
   b.arg("dout", dout, BF16, oshape);
   b.arg("lse", lse, F32, {B, Hq, S});
-  return {(int)B, (int)Hq, (int)Hkv, (int)S};
+  return {(int)B, (int)Hq, (int)Hkv, (int)S, (int)Sk};
 }
 static_assert(FB_D == FF_D, "tuned attention kernels share D");
 
@@ -696,15 +704,25 @@ static_assert(FB_D == FF_D, "tuned attention kernels share D");
 // segment_ids [B,S] int32 (packed documents = maximal runs of equal ids): the
 // pre-pass turns them into bounds [B,2,S] (run start, run end), the SEG
 // forward masks with them, and bounds is returned third for fa_bwd2.
+// causal=False: no mask and k/v of their own length (fa_fwd_full_bf16).
 std::vector<at::Tensor> fa_fwd_impl(const Binding& b, int64_t mode, at::Tensor q,
                                     at::Tensor k, at::Tensor v, double scale,
-                                    bool out_bshd, const OptTensor& segment_ids = {}) {
-  FaShape s = fa_check(b, FF_QTILE, q, k, v);
+                                    bool out_bshd, const OptTensor& segment_ids = {},
+                                    bool causal = true) {
+  TORCH_CHECK(causal || !segment_ids.has_value(), b.fn, ": causal=False takes no segment_ids: ",
+              "documents are causal runs");
+  FaShape s = fa_check(b, FF_QTILE, q, k, v, {}, {}, {}, false, causal);
   TORCH_CHECK(!out_bshd || (int64_t)s.Hq * FF_D <= INT_MAX, b.fn,
               ": Hq * 128 must fit int in the [B,S,Hq,D] layout");
   b.arg("segment_ids", segment_ids, I32, {s.B, s.S});
   auto out = out_bshd ? at::empty({s.B, s.S, s.Hq, FF_D}, q.options()) : at::empty_like(q);
   auto lse = at::empty({s.B, s.Hq, s.S}, q.options().dtype(F32));
+  if (!causal) {
+    b.launch(fa_fwd_full_bf16, dim3(s.S / FF_QTILE, s.Hq, s.B), FF_THREADS, bf16(q), bf16(k),
+             bf16(v), bf16_mut(out), lse.data_ptr<float>(), s.B, s.Hq, s.Hkv, s.S, s.Sk,
+             (float)scale, out_bshd ? 1 : 0);
+    return {out, lse};
+  }
   if (segment_ids.has_value()) {
     auto bounds = at::empty({s.B, 2, s.S}, q.options().dtype(I32));
     b.launch(fa_seg_bounds_i32, dim3((s.S + FF_SEG_THREADS - 1) / FF_SEG_THREADS, s.B),
@@ -723,8 +741,9 @@ std::vector<at::Tensor> fa_fwd_impl(const Binding& b, int64_t mode, at::Tensor q
 }
 
 std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
-                               bool out_bshd, OptTensor segment_ids) {
-  return fa_fwd_impl(Binding("fa_fwd", "q", q), 0, q, k, v, scale, out_bshd, segment_ids);
+                               bool out_bshd, OptTensor segment_ids, bool causal) {
+  return fa_fwd_impl(Binding("fa_fwd", "q", q), 0, q, k, v, scale, out_bshd, segment_ids,
+                     causal);
 }
 
 std::vector<at::Tensor> fa_fwd_ablate(at::Tensor q, at::Tensor k, at::Tensor v,
@@ -736,21 +755,27 @@ std::vector<at::Tensor> fa_fwd_ablate(at::Tensor q, at::Tensor k, at::Tensor v,
   return fa_fwd_impl(Binding("fa_fwd_ablate", "q", q), mode, q, k, v, scale, false);
 }
 
-// delta[b,h,s] = sum_d dout * o for fa_bwd2; bshd: dout and o are [B,S,Hq,D]
+// delta[b,h,s] = sum_d dout * o for fa_bwd2; bshd: dout and o are [B,S,Hq,D].
+// With dlse [B,Hq,S], the cotangent of lse: delta - dlse (attention_bwd2.hip).
 at::Tensor fa_bwd_delta(const Binding& b, const FaShape& s, const at::Tensor& dout,
-                        const at::Tensor& o, bool bshd = false) {
+                        const at::Tensor& o, bool bshd = false, const OptTensor& dlse = {}) {
   auto delta = at::empty({s.B, s.Hq, s.S}, o.options().dtype(F32));
   int64_t rows = (int64_t)s.B * s.Hq * s.S;
-  b.launch(fa_bwd_preprocess, grid_for(rows, 1, 4096), 256, bf16(dout), bf16(o),
-           delta.data_ptr<float>(), rows, s.Hq, s.S, bshd ? 1 : 0);
+  if (dlse.has_value())
+    b.launch(fa_bwd_preprocess_dlse, grid_for(rows, 1, 4096), 256, bf16(dout), bf16(o),
+             (const float*)dlse->data_ptr<float>(), delta.data_ptr<float>(), rows, s.Hq, s.S,
+             bshd ? 1 : 0);
+  else
+    b.launch(fa_bwd_preprocess, grid_for(rows, 1, 4096), 256, bf16(dout), bf16(o),
+             delta.data_ptr<float>(), rows, s.Hq, s.S, bshd ? 1 : 0);
   return delta;
 }
 
-// [B,Hq,S,D] per-q-head partial -> [B,Hkv,S,D] (identity when Hkv == Hq)
+// [B,Hq,Sk,D] per-q-head partial -> [B,Hkv,Sk,D] (identity when Hkv == Hq)
 at::Tensor fa_bwd_reduce(const Binding& b, const FaShape& s, const at::Tensor& part) {
   if (s.Hkv == s.Hq) return part;
-  auto out = at::empty({s.B, s.Hkv, s.S, FF_D}, part.options());
-  int64_t SD = (int64_t)s.S * FF_D;
+  auto out = at::empty({s.B, s.Hkv, s.Sk, FF_D}, part.options());
+  int64_t SD = (int64_t)s.Sk * FF_D;
   b.launch(fa_bwd_reduce_gqa, grid_for((int64_t)s.B * s.Hkv * SD / 8, 256), 256,
            bf16(part), bf16_mut(out), s.B, s.Hq, s.Hkv, SD);
   return out;
@@ -759,28 +784,53 @@ at::Tensor fa_bwd_reduce(const Binding& b, const FaShape& s, const at::Tensor& p
 // ------------------------------ flash-attention backward v2 ---------------
 std::vector<at::Tensor> fa_bwd2(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                 at::Tensor dout, at::Tensor lse, double scale,
-                                bool fused_dvdk, bool bshd, OptTensor seg_bounds) {
+                                bool fused_dvdk, bool bshd, OptTensor seg_bounds, bool causal,
+                                OptTensor dlse) {
   // 32x32-MFMA backward (attention_bwd2.hip): preprocess + dq + dv + dk
   // (+ GQA reduction); lse ln-domain.  bshd: o and dout are [B,S,Hq,D] (the
   // split kernels only); dq/dk/dv are [B,H,S,D] either way.  seg_bounds
   // [B,2,S] int32, the third result of fa_fwd(.., segment_ids=): the SEG dq,
   // dv and dk kernels (split only).  The kernels hold every tile index they
   // derive from its content to the range of the unmasked kernels.
+  // causal=False: the FULL kernels, k/v [B,Hkv,Sk,D] of their own length (split
+  // only, no seg_bounds).  dlse [B,Hq,S] fp32: the cotangent of lse, folded into
+  // delta by the pre-pass; any form of the kernels takes it.
   Binding b("fa_bwd2", "q", q);
+  TORCH_CHECK(causal || !seg_bounds.has_value(), "fa_bwd2: causal=False takes no seg_bounds: ",
+              "documents are causal runs");
+  TORCH_CHECK(causal || !fused_dvdk, "fa_bwd2: the fused dv+dk kernel is causal: ",
+              "causal=False needs fused_dvdk=False");
   TORCH_CHECK(!(bshd && fused_dvdk), "fa_bwd2: the fused dv+dk kernel reads [B,Hq,S,D] ",
               "only: bshd=True needs fused_dvdk=False");
   TORCH_CHECK(!(seg_bounds.has_value() && fused_dvdk), "fa_bwd2: the fused dv+dk kernel has ",
               "no segment mask: seg_bounds needs fused_dvdk=False");
-  FaShape s = fa_check(b, FB_TILE, q, k, v, o, dout, lse, bshd);
+  FaShape s = fa_check(b, FB_TILE, q, k, v, o, dout, lse, bshd, causal);
   b.arg("seg_bounds", seg_bounds, I32, {s.B, 2, s.S});
+  b.arg("dlse", dlse, F32, {s.B, s.Hq, s.S});
   const int* pb = seg_bounds.has_value() ? seg_bounds->data_ptr<int>() : nullptr;
   // the kernels write -inf into the masked scores BEFORE scaling them
   // (ff_mask): only a positive finite scale keeps them -inf
   TORCH_CHECK(scale > 0 && std::isfinite(scale), b.fn, ": scale = ", scale,
               " must be positive and finite");
-  auto delta = fa_bwd_delta(b, s, dout, o, bshd);
+  auto delta = fa_bwd_delta(b, s, dout, o, bshd, dlse);
   auto dq = at::empty_like(q);
   dim3 grid(s.S / FB_TILE, s.Hq, s.B);
+  if (!causal) {
+    b.launch(fa2_dq_full_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+             lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), s.B, s.Hq, s.Hkv,
+             s.S, s.Sk, (float)scale, bshd ? 1 : 0);
+    // dv and dk own kv rows: their grid and their per-Hq partials follow Sk
+    dim3 kgrid(s.Sk / FB_TILE, s.Hq, s.B);
+    auto dv_full = at::empty({s.B, s.Hq, s.Sk, FF_D}, q.options());
+    auto dk_full = at::empty({s.B, s.Hq, s.Sk, FF_D}, q.options());
+    b.launch(fa2_dv_full_bf16, kgrid, FB_THREADS, bf16(q), bf16(k), bf16(dout),
+             lse.data_ptr<float>(), bf16_mut(dv_full), s.B, s.Hq, s.Hkv, s.S, s.Sk,
+             (float)scale, bshd ? 1 : 0);
+    b.launch(fa2_dk_full_bf16, kgrid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
+             lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dk_full), s.B, s.Hq,
+             s.Hkv, s.S, s.Sk, (float)scale, bshd ? 1 : 0);
+    return {dq, fa_bwd_reduce(b, s, dk_full), fa_bwd_reduce(b, s, dv_full)};
+  }
   if (pb)
     b.launch(fa2_dq_seg_bf16, grid, FB_THREADS, bf16(q), bf16(k), bf16(v), bf16(dout),
              lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_mut(dq), pb, s.B, s.Hq,
@@ -1047,10 +1097,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_bwd2", &fa_bwd2, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
         pybind11::arg("o"), pybind11::arg("dout"), pybind11::arg("lse"),
         pybind11::arg("scale"), pybind11::arg("fused_dvdk"), pybind11::arg("bshd") = false,
-        pybind11::arg("seg_bounds") = pybind11::none());
+        pybind11::arg("seg_bounds") = pybind11::none(), pybind11::arg("causal") = true,
+        pybind11::arg("dlse") = pybind11::none());
   m.def("fa_fwd", &fa_fwd, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
         pybind11::arg("scale"), pybind11::arg("out_bshd") = false,
-        pybind11::arg("segment_ids") = pybind11::none());
+        pybind11::arg("segment_ids") = pybind11::none(), pybind11::arg("causal") = true);
   m.def("fa_fwd_ablate", &fa_fwd_ablate);
   m.def("fa_gen_fwd", &fa_gen_fwd, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("causal"),

@@ -56,10 +56,13 @@ struct ff_ctx {
   int tid, lane, wave;
   int l31, half;         // lane & 31, lane >> 5
   int tile, h, b;        // remapped blockIdx.x / .y / .z
-  int64_t rbase;         // ((b*Hq + h) * S): row base into lse / delta
+  int64_t rbase;         // ((b*Hq + h) * Sq): row base into lse / delta
   int64_t qbase, kbase;  // element base of this head in q-shaped / k-shaped tensors
 };
-DEV ff_ctx ff_prologue(int Hq, int Hkv, int S) {
+// Sq rows per head in q, o, dout, lse, delta and dq, Sk in k and v.  The causal
+// kernels are square and pass their S twice; only the FULL instantiations have
+// two lengths.
+DEV ff_ctx ff_prologue(int Hq, int Hkv, int Sq, int Sk) {
   ff_ctx c;
   c.tid = threadIdx.x;
   c.lane = c.tid & 63;
@@ -72,9 +75,9 @@ DEV ff_ctx ff_prologue(int Hq, int Hkv, int S) {
   c.h = by;
   c.b = bz;
   const int hkv = c.h / (Hq / Hkv);
-  c.rbase = ((int64_t)c.b * Hq + c.h) * S;
+  c.rbase = ((int64_t)c.b * Hq + c.h) * Sq;
   c.qbase = c.rbase * FF_D;
-  c.kbase = (((int64_t)c.b * Hkv + hkv) * S) * FF_D;
+  c.kbase = (((int64_t)c.b * Hkv + hkv) * Sk) * FF_D;
   return c;
 }
 

@@ -534,7 +534,9 @@ def vocab_parallel_cross_entropy(
 # Tuned flash attention: our CDNA4 MFMA forward (ops/csrc/attention_fwd.hip,
 # returns logsumexp) + backward (ops/csrc/attention_bwd2.hip); causal,
 # head_dim 128, GQA, seq % 256 == 0; optionally the packed-document mask of
-# flash_attention(..., contiguous_segments=True).
+# flash_attention(..., contiguous_segments=True).  _FlashAttentionLse below
+# runs the same family without a mask (Sq != Sk allowed) and with a
+# differentiable lse.
 # ---------------------------------------------------------------------------
 class _FlashAttention(torch.autograd.Function):
     """Causal flash attention, fully on our MFMA kernels: fa_fwd
@@ -600,6 +602,51 @@ class _FlashAttention(torch.autograd.Function):
         if not dout.is_contiguous():
             dout = dout.contiguous()
         dq, dk, dv = _ext().fa_bwd2(q, k, v, out, dout, lse, ctx.scale, False, bshd=True)
+        return dq, dk, dv, None, None
+
+
+# VESCALE_FA_FULL selects where flash_attention sends the D=128 calls that the
+# tuned family serves beyond causal self-attention without an lse (non-causal,
+# Sq != Sk, return_lse):
+#   tuned  the 32x32 kernels: FULL instantiations, fa_bwd_preprocess_dlse
+#   gen    the general 16x16 kernels (attention_gen.hip), as before: A/B, fallback
+# The default follows tools/fa_full_bench.py (profiles/fa32_full.txt): tuned is
+# the default only while it beats gen at all three shapes measured there.
+FA_FULL_DEFAULT = "tuned"
+
+
+def _fa_full_backend():
+    backend = os.environ.get("VESCALE_FA_FULL", FA_FULL_DEFAULT)
+    if backend not in ("tuned", "gen"):
+        raise ValueError(f"VESCALE_FA_FULL = {backend!r} must be 'tuned' or 'gen'")
+    return backend
+
+
+class _FlashAttentionLse(torch.autograd.Function):
+    """The tuned D=128 kernels with two differentiable outputs (out, lse),
+    [B, H, S, D] throughout: fa_fwd / fa_bwd2 with causal=False (the FULL
+    kernels: no mask, k/v of their own length Sk) or causal=True (the causal
+    kernels _FlashAttention runs, here with the lse handed out).  The lse's
+    cotangent reaches the kernels through the delta pre-pass (dS = P * (dP -
+    (delta - dlse))); a missing dout is zeros, a missing dlse no dlse."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, causal):
+        out, lse = _ext().fa_fwd(q, k, v, scale, causal=causal)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.args = (scale, causal)
+        ctx.set_materialize_grads(False)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, dlse):
+        q, k, v, out, lse = ctx.saved_tensors
+        scale, causal = ctx.args
+        dout = torch.zeros_like(out) if dout is None else dout.contiguous()
+        if dlse is not None:
+            dlse = dlse.float().contiguous()
+        dq, dk, dv = _ext().fa_bwd2(q, k, v, out, dout, lse, scale, False,
+                                    causal=causal, dlse=dlse)
         return dq, dk, dv, None, None
 
 
@@ -828,8 +875,19 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
     Dispatch: (1) the tuned D=128 causal kernels when their gate holds, no
     lse is wanted and there are no segment ids, or the ids come with
     contiguous_segments, and there is no window (the tuned kernels have no
-    band mask: a call with a window never takes them); (2) the general HIP kernel
-    for bf16 on GPU with D in {64, 128}; (3) the torch reference (CPU, other
+    band mask: a call with a window never takes them); (1b) the same family
+    for bf16 on GPU with D == 128, no window (or one that masks nothing
+    beyond is_causal: left >= Sq - 1 + causal_shift and right folded into
+    is_causal, so that a neutral window gives the bits of no window), no
+    segment ids and Sq and Sk
+    positive multiples of 256: any call without is_causal (the FULL kernels:
+    no mask, Sq and Sk independent, with or without return_lse), and
+    is_causal with causal_shift == 0, Sq == Sk and return_lse (the causal
+    kernels, lse handed out and differentiable); VESCALE_FA_FULL=gen keeps
+    these calls on the general kernels (A/B, fallback); (2) the general HIP
+    kernel for bf16 on GPU with D in {64, 128}: shifted causal masks, windows,
+    segment ids without contiguous_segments (and with it when an lse is
+    wanted), D = 64, ragged lengths; (3) the torch reference (CPU, other
     dtypes / head dims, VESCALE_FA=aten)."""
     import math
 
@@ -868,6 +926,20 @@ def flash_attention(q, k, v, *, is_causal=False, causal_shift=0, scale=None,
         return _FlashAttention.apply(
             q.contiguous(), k.contiguous(), v.contiguous(), scale, q_seg
         )
+    # the tuned family beyond that: no mask at all with any two lengths (the
+    # FULL kernels), or the causal kernels with the lse handed out.  By the
+    # mask, not by its spelling: (causal, shift, lower) are the kernels' own
+    # terms, and a lower bound j >= i + lower that no pair (i, j) violates
+    # (left >= Sq - 1 + shift) is no band, so such a call is, bit for bit, the
+    # call without a window.
+    no_band = lower is None or lower <= -(Sq - 1)
+    if (hip and D == 128 and no_band and q_seg is None
+            and Sq > 0 and Sk > 0 and Sq % 256 == 0 and Sk % 256 == 0
+            and (not causal or (shift == 0 and Sq == Sk and return_lse))
+            and _fa_full_backend() == "tuned"):
+        out, lse = _FlashAttentionLse.apply(
+            q.contiguous(), k.contiguous(), v.contiguous(), float(scale), causal)
+        return (out, lse) if return_lse else out
     if contiguous_segments:
         q_seg = kv_seg = _run_start_ids(q_seg)
     if hip:
