@@ -19,6 +19,7 @@
 //
 // Requires M%256==0, N%256==0, K%64==0 (the training GEMM shapes).
 #include "common.h"
+#include "gemm8_sched.h"
 
 #define G8_BM 256
 #define G8_BN 256
@@ -224,6 +225,16 @@ gemm8_tn_bf16_lockstep(const unsigned short* A, const unsigned short* B,
 // Counted waits (outstanding global_load_lds instructions per wave):
 //   p0: vmcnt(4)  — youngest allowed: prev p1 (A q1, 2) + prev p2 (A q0, 2)
 //   p2: vmcnt(8)  — youngest: this p0 (4) + p1 (2) + prev p2 (2)
+// Those counts hold while every slot they allow to stay in flight was issued.
+// TAIL RULE: on the last tile m = ntile-1 the slot (m-1).p2 (A(m+1) q0) was
+// never issued and m.p0, m.p1 issue nothing, so the queue is 2 loads shorter
+// at p0 and holds only A(m)q1 at p2; vmcnt(4) would leave B(m) h1 in flight
+// under the reads of waves 2,3,6,7 and vmcnt(8) would leave A(m)q1 in flight
+// under phases 2,3.  The last tile therefore waits vmcnt(2) at p0 and
+// vmcnt(0) at p2.  The slot table, the counts and this rule (and their RA,
+// rot8 and rot9 forms) live in gemm8_sched.h, which the host model
+// tests/gemm8_wait_model.cpp walks, one wave's queue, for every schedule and
+// tile count.
 // Safety: per-phase barrier PAIRS bound wave skew so no wave can issue a
 // prefetch into a region while another wave's ds_reads of it are pending —
 // each phase's ds_reads complete (compiler lgkm waits) before its MFMAs,
@@ -248,13 +259,54 @@ DEV void g8_prefetch_quarter(const unsigned short* __restrict__ g, int ld,
       (__attribute__((address_space(3))) void*)lb, 16, 0, 0);
 }
 
+// s_waitcnt takes its count as an immediate: a ladder over the counts the
+// schedule tables of gemm8_sched.h produce; n < 0 = no wait
+#define G8_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")")
+DEV void g8_wait(int n) {
+  if (n < 0) return;
+  if (n >= 8) { G8_VMCNT(8); }
+  else if (n >= 6) { G8_VMCNT(6); }
+  else if (n >= 4) { G8_VMCNT(4); }
+  else if (n >= 2) { G8_VMCNT(2); }
+  else { G8_VMCNT(0); }
+}
+
+// issue one slot of gemm8_sched.h: the regions of K-tile s.tile, into the
+// A / B buffers lAt / lBt ([half][128 x 64]) that tile lives in.
+// Ag and Bg carry NO __restrict__ on purpose.  With it the loads get alias
+// scopes, and the compiler drops the vmcnt(0) it otherwise puts in front of
+// the LDS reads of nearly every phase of rot8 and rot9
+// (profiles/gemm8_waits_isa.txt).  Those two kernels depend on that drain:
+// built without it, rot8 summed stale rows at 4 K-tiles on an MI355X,
+// although each wave's own counted waits are right (a wave's wait covers its
+// own loads only, and a phase reads straight after it, before the next
+// barrier).  The rot kernels' steady loop has no such compiler wait.
+template <int SWZ>
+DEV void g8_issue(G8Slot s, const unsigned short* Ag, const unsigned short* Bg, int K,
+                  unsigned short (*lAt)[128 * G8_BK],
+                  unsigned short (*lBt)[128 * G8_BK], int tid) {
+  if (s.tile < 0) return;
+  const unsigned short* At = Ag + (int64_t)s.tile * G8_BK;
+  const unsigned short* Bt = Bg + (int64_t)s.tile * G8_BK;
+  if (s.regions & G8S_BH0) g8_prefetch_half<SWZ>(Bt, K, lBt[0], tid);
+  if (s.regions & G8S_BH1) g8_prefetch_half<SWZ>(Bt + (int64_t)128 * K, K, lBt[1], tid);
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    if (s.regions & (q ? G8S_AQ1 : G8S_AQ0)) {
+      g8_prefetch_quarter<SWZ>(At, K, lAt[0], q, tid);
+      g8_prefetch_quarter<SWZ>(At + (int64_t)128 * K, K, lAt[1], q, tid);
+    }
+}
+
 // RA (read-ahead): each phase's operand frags are ds_read during the
 // PREVIOUS phase's MFMA burst into the alternate register set, so LDS
 // latency overlaps the matrix pipe (the fine ds||MFMA interleave of m196).
 // Safety: a region overwrite may only issue one full phase after the
 // lgkmcnt(0) that drained its readers (all waves provably past it once
 // they pass that phase's closing barrier); waits shift one phase early:
-// vmcnt(6) at p1 (A q1), vmcnt(4) at p3 (B pair + A q0 of the next tile).
+// vmcnt(6) at p1 (A q1), vmcnt(4) at p3 (B pair + A q0 of the next tile);
+// by the tail rule vmcnt(2) at the p3 before the last tile and vmcnt(0) at
+// the last tile's p1.
 template <int SWZ, bool PRIO = true, bool U2 = false, bool RA = false>
 DEV void g8_body_rot(const unsigned short* __restrict__ A,
                      const unsigned short* __restrict__ B,
@@ -298,16 +350,9 @@ DEV void g8_body_rot(const unsigned short* __restrict__ A,
   g8_prefetch_half<SWZ>(Bg + (int64_t)128 * K, K, lB[0][1], tid);
   asm volatile("s_waitcnt vmcnt(0)");
   __builtin_amdgcn_s_barrier();
-  if (ntile > 1) {
-    const unsigned short* A1 = Ag + G8_BK;
-    const unsigned short* B1 = Bg + G8_BK;
-    g8_prefetch_half<SWZ>(B1, K, lB[1][0], tid);
-    g8_prefetch_half<SWZ>(B1 + (int64_t)128 * K, K, lB[1][1], tid);
-    g8_prefetch_quarter<SWZ>(A1, K, lA[1][0], 0, tid);
-    g8_prefetch_quarter<SWZ>(A1 + (int64_t)128 * K, K, lA[1][1], 0, tid);
-    g8_prefetch_quarter<SWZ>(A1, K, lA[1][0], 1, tid);
-    g8_prefetch_quarter<SWZ>(A1 + (int64_t)128 * K, K, lA[1][1], 1, tid);
-  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    g8_issue<SWZ>(g8s_rot_prologue_slot(i, ntile), Ag, Bg, K, lA[1], lB[1], tid);
 
   g8_shortx8 afr[2][4], bfr[2][4];
   if constexpr (RA) {
@@ -327,24 +372,19 @@ DEV void g8_body_rot(const unsigned short* __restrict__ A,
    for (int sub = 0; sub < (U2 ? 2 : 1); ++sub) {
     const int kt = kt0 + sub;
     const int buf = U2 ? sub : (kt & 1);
-    const unsigned short* A1 = Ag + (int64_t)(kt + 1) * G8_BK;  // tile m+1
-    const unsigned short* B1 = Bg + (int64_t)(kt + 1) * G8_BK;
-    const unsigned short* A2 = Ag + (int64_t)(kt + 2) * G8_BK;  // tile m+2
 
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int kc = p & 1;
       const int mh2 = p >> 1;
 
-      if constexpr (!RA) {
-        // counted boundary waits (see header comment)
-        if (p == 0 && kt >= 1) asm volatile("s_waitcnt vmcnt(4)");
-        if (p == 2 && kt >= 1) asm volatile("s_waitcnt vmcnt(8)");
-      } else {
-        // RA: waits gate the read-AHEAD issued later this phase
-        if (p == 1 && kt >= 1) asm volatile("s_waitcnt vmcnt(6)");
-        if (p == 3) asm volatile("s_waitcnt vmcnt(4)");
-      }
+      // counted boundary waits (see header comment).  A wave's wait covers
+      // its own loads, and every region is filled by all eight waves, so a
+      // barrier must lie between the wait and the reads it gates.  RA: the
+      // wait opens the phase and gates the read-AHEAD issued after this
+      // phase's first barrier.  Otherwise the wait for phase p sits at the end
+      // of the phase before, in front of its closing barrier (below).
+      if constexpr (RA) g8_wait(g8s_rot_wait(true, p, kt, ntile));
       asm volatile("" ::: "memory");
 
       // (a) ds-reads for this phase's 16 mfmas (RA: already in regs)
@@ -358,19 +398,11 @@ DEV void g8_body_rot(const unsigned short* __restrict__ A,
               g8_frag<SWZ>(lB[buf][bh], wn * 4 - bh * 8 + j, kc, lane);
       }
 
-      // (b) this phase's prefetch slot
-      if (p == 0 && kt >= 1 && kt + 1 < ntile) {
-        g8_prefetch_half<SWZ>(B1, K, lB[buf ^ 1][0], tid);
-        g8_prefetch_half<SWZ>(B1 + (int64_t)128 * K, K, lB[buf ^ 1][1], tid);
-      } else if (p == 1 && kt >= 1 && kt + 1 < ntile) {
-        g8_prefetch_quarter<SWZ>(A1, K, lA[buf ^ 1][0], 1, tid);
-        g8_prefetch_quarter<SWZ>(A1 + (int64_t)128 * K, K, lA[buf ^ 1][1], 1, tid);
-      } else if (p == 2 && kt + 2 < ntile) {
-        // A(m+2) q0 -> buf b (A(m) q0 died at m.p1); this slot also covers
-        // A(m+1) q0, issued one tile earlier at (m-1).p2
-        g8_prefetch_quarter<SWZ>(A2, K, lA[buf][0], 0, tid);
-        g8_prefetch_quarter<SWZ>(A2 + (int64_t)128 * K, K, lA[buf][1], 0, tid);
-      }
+      // (b) this phase's prefetch slot: p0 B(m+1) -> buf b^1, p1 A(m+1) q1
+      // -> buf b^1, p2 A(m+2) q0 -> buf b (A(m) q0 died at m.p1; this slot
+      // also covers A(m+1) q0, issued one tile earlier at (m-1).p2)
+      g8_issue<SWZ>(g8s_rot_slot(p, kt, ntile), Ag, Bg, K,
+                    lA[p == 2 ? buf : buf ^ 1], lB[buf ^ 1], tid);
 
       // (c) lockstep: barrier pair around the MFMA burst (m196: required
       // once prefetches overwrite regions of the buffer being read)
@@ -404,6 +436,13 @@ DEV void g8_body_rot(const unsigned short* __restrict__ A,
             bfr[np & 1][j] =
                 g8_frag<SWZ>(lB[nbuf][bh], wn * 4 - bh * 8 + j, nkc, lane);
         }
+      }
+      if constexpr (!RA) {
+        // the wait that gates the NEXT phase's reads: the queue does not
+        // change between here and that phase, so the counts are the table's,
+        // and the closing barrier publishes what every wave has waited for
+        const int nkt = kt + (p == 3 ? 1 : 0);
+        if (nkt < ntile) g8_wait(g8s_rot_wait(false, (p + 1) & 3, nkt, ntile));
       }
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -550,9 +589,8 @@ DEV void g8_body_rot8(const unsigned short* __restrict__ A,
       const int mh2 = p >> 1;
       const int kt = T + buf;
 
-      // counted waits: the iteration's two drain points
-      if (gp == 0 && T >= 2) asm volatile("s_waitcnt vmcnt(2)");
-      if (gp == 4 && T >= 2) asm volatile("s_waitcnt vmcnt(2)");
+      // (the counted waits for this phase's reads sit in front of the
+      // closing barrier of the phase before, see below)
       asm volatile("" ::: "memory");
 
       // this phase's operand frags
@@ -564,52 +602,10 @@ DEV void g8_body_rot8(const unsigned short* __restrict__ A,
       for (int j = 0; j < 4; ++j)
         bf[j] = g8_frag<SWZ>(lB[buf][bh], wn * 4 - bh * 8 + j, kc, lane);
 
-      // slot table (see header)
-      switch (gp) {
-        case 0:
-          // T==0: tile 1 was fully staged by the prologue
-          if (T >= 2 && T + 1 < ntile) {
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 1) * G8_BK, K, lA[1][0], 1, tid);
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 1) * G8_BK + (int64_t)128 * K, K, lA[1][1], 1, tid);
-          }
-          break;
-        case 1:
-          if (T >= 2 && T + 1 < ntile) {
-            g8_prefetch_half<SWZ>(Bg + (int64_t)(T + 1) * G8_BK, K, lB[1][0], tid);
-          }
-          break;
-        case 2:
-          if (T >= 2 && T + 1 < ntile) {
-            g8_prefetch_half<SWZ>(Bg + (int64_t)(T + 1) * G8_BK + (int64_t)128 * K, K, lB[1][1], tid);
-          }
-          break;
-        case 3:
-          if (T + 2 < ntile) {
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 2) * G8_BK, K, lA[0][0], 0, tid);
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 2) * G8_BK + (int64_t)128 * K, K, lA[0][1], 0, tid);
-          }
-          break;
-        case 4:
-          if (T + 2 < ntile) {
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 2) * G8_BK, K, lA[0][0], 1, tid);
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 2) * G8_BK + (int64_t)128 * K, K, lA[0][1], 1, tid);
-          }
-          break;
-        case 5:
-          if (T + 2 < ntile)
-            g8_prefetch_half<SWZ>(Bg + (int64_t)(T + 2) * G8_BK, K, lB[0][0], tid);
-          break;
-        case 6:
-          if (T + 2 < ntile)
-            g8_prefetch_half<SWZ>(Bg + (int64_t)(T + 2) * G8_BK + (int64_t)128 * K, K, lB[0][1], tid);
-          break;
-        case 7:
-          if (T + 3 < ntile) {
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 3) * G8_BK, K, lA[1][0], 0, tid);
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 3) * G8_BK + (int64_t)128 * K, K, lA[1][1], 0, tid);
-          }
-          break;
-      }
+      // slot table (see header): gp0..2 stage tile T+1 into buf 1, gp3..6
+      // tile T+2 into buf 0, gp7 tile T+3 into buf 1
+      g8_issue<SWZ>(g8s_rot89_slot(false, gp, T, ntile), Ag, Bg, K,
+                    lA[(gp >= 3 && gp <= 6) ? 0 : 1], lB[(gp >= 3 && gp <= 6) ? 0 : 1], tid);
 
       // lockstep barrier pair around the MFMA burst
       __builtin_amdgcn_s_barrier();
@@ -620,6 +616,12 @@ DEV void g8_body_rot8(const unsigned short* __restrict__ A,
         for (int j = 0; j < 4; ++j)
           acc[mh2 * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               af[i], bf[j], acc[mh2 * 4 + i][j], 0, 0, 0);
+      {
+        // counted wait gating the NEXT phase's reads, published to the other
+        // waves by the closing barrier (as in g8_body_rot)
+        const int nT = T + (gp == 7 ? 2 : 0);
+        if (nT < ntile) g8_wait(g8s_rot89_wait(false, (gp + 1) & 7, nT, ntile));
+      }
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();
       (void)kt;
@@ -751,7 +753,8 @@ DEV void g8_body_rot9(const unsigned short* __restrict__ A,
       const unsigned short* lAband = lA[(T + abuf) & 1][wm];
       const unsigned short* lBband = lB[gp < 4 ? bT : bT1][bh];
 
-      if ((gp == 0 || gp == 4) && T >= 2) asm volatile("s_waitcnt vmcnt(6)");
+      // (the counted waits for this phase's reads sit in front of the
+      // closing barrier of the phase before, see below)
       asm volatile("" ::: "memory");
 
       g8_shortx8 af[4], bf[4];
@@ -762,48 +765,12 @@ DEV void g8_body_rot9(const unsigned short* __restrict__ A,
       for (int j = 0; j < 4; ++j)
         bf[j] = g8_frag<SWZ>(lBband, wn * 4 - bh * 8 + j, kc, lane);
 
-      switch (gp) {
-        case 0:  // A(T+1)q1 (prologue covered T==0)
-          if (T >= 2 && T + 1 < ntile) {
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 1) * G8_BK, K, lA[(T + 1) & 1][0], 1, tid);
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 1) * G8_BK + (int64_t)128 * K, K, lA[(T + 1) & 1][1], 1, tid);
-          }
-          break;
-        case 1:
-          if (T + 2 < ntile)
-            g8_prefetch_half<SWZ>(Bg + (int64_t)(T + 2) * G8_BK, K, lB[bT2][0], tid);
-          break;
-        case 2:
-          if (T + 2 < ntile)
-            g8_prefetch_half<SWZ>(Bg + (int64_t)(T + 2) * G8_BK + (int64_t)128 * K, K, lB[bT2][1], tid);
-          break;
-        case 3:
-          if (T + 2 < ntile) {
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 2) * G8_BK, K, lA[T & 1][0], 0, tid);
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 2) * G8_BK + (int64_t)128 * K, K, lA[T & 1][1], 0, tid);
-          }
-          break;
-        case 4:
-          if (T + 2 < ntile) {
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 2) * G8_BK, K, lA[T & 1][0], 1, tid);
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 2) * G8_BK + (int64_t)128 * K, K, lA[T & 1][1], 1, tid);
-          }
-          break;
-        case 5:
-          if (T + 3 < ntile)
-            g8_prefetch_half<SWZ>(Bg + (int64_t)(T + 3) * G8_BK, K, lB[bT][0], tid);
-          break;
-        case 6:
-          if (T + 3 < ntile)
-            g8_prefetch_half<SWZ>(Bg + (int64_t)(T + 3) * G8_BK + (int64_t)128 * K, K, lB[bT][1], tid);
-          break;
-        case 7:
-          if (T + 3 < ntile) {
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 3) * G8_BK, K, lA[(T + 1) & 1][0], 0, tid);
-            g8_prefetch_quarter<SWZ>(Ag + (int64_t)(T + 3) * G8_BK + (int64_t)128 * K, K, lA[(T + 1) & 1][1], 0, tid);
-          }
-          break;
-      }
+      // slot table (see header).  A: gp0, gp7 stage tiles T+1, T+3 into
+      // lA[(T+1)&1], gp3, gp4 tile T+2 into lA[T&1].  B: gp1, gp2 stage tile
+      // T+2 into bT2, gp5, gp6 tile T+3 into bT (B(T) died at gp3)
+      g8_issue<SWZ>(g8s_rot89_slot(true, gp, T, ntile), Ag, Bg, K,
+                    lA[(gp == 3 || gp == 4) ? (T & 1) : ((T + 1) & 1)],
+                    lB[gp < 4 ? bT2 : bT], tid);
 
       __builtin_amdgcn_s_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)");
@@ -813,6 +780,12 @@ DEV void g8_body_rot9(const unsigned short* __restrict__ A,
         for (int j = 0; j < 4; ++j)
           acc[mh2 * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               af[i], bf[j], acc[mh2 * 4 + i][j], 0, 0, 0);
+      {
+        // counted wait gating the NEXT phase's reads, published to the other
+        // waves by the closing barrier (as in g8_body_rot)
+        const int nT = T + (gp == 7 ? 2 : 0);
+        if (nT < ntile) g8_wait(g8s_rot89_wait(true, (gp + 1) & 7, nT, ntile));
+      }
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();
     }
