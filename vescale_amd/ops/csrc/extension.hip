@@ -20,6 +20,7 @@
 #include "philox_random.hip"
 #include "gemm.hip"
 #include "gemm8.hip"
+#include "gemm_fp8.hip"
 #include "gemm_grouped.hip"
 #include "attention_fwd.hip"
 #include "attention_bwd2.hip"
@@ -38,6 +39,8 @@ constexpr auto BF16 = at::kBFloat16;
 constexpr auto F32 = at::kFloat;
 constexpr auto I64 = at::kLong;
 constexpr auto I32 = at::kInt;
+constexpr auto E4M3 = at::kFloat8_e4m3fn;
+constexpr auto E5M2 = at::kFloat8_e5m2;
 using OptTensor = c10::optional<at::Tensor>;
 
 // typed pointers (bf16 travels as unsigned short); an absent optional is null
@@ -634,16 +637,130 @@ at::Tensor gemm_operand_t(const Binding& b, const at::Tensor& a, const Weights& 
   return out;
 }
 
+// ------------------------------ fp8 GEMM and quantisers (gemm_fp8.hip) ------
+inline bool is_fp8(const at::Tensor& t) {
+  return t.scalar_type() == E4M3 || t.scalar_type() == E5M2;
+}
+inline unsigned char* u8_mut(const OptTensor& t) {
+  return t.has_value() ? reinterpret_cast<unsigned char*>(t->data_ptr()) : nullptr;
+}
+
+// The quantiser forms take one operand, like group_form = "transpose".
+void fp8_one_operand(const Binding& b, const std::string& form, const at::Tensor& a,
+                     const Weights& bw, int64_t mode) {
+  const auto* list = std::get_if<std::vector<at::Tensor>>(&bw);
+  TORCH_CHECK(list && list->empty(), b.fn, ": group_form = '", form,
+              "' takes one operand: b must be []");
+  TORCH_CHECK(mode == 0, b.fn, ": group_form = '", form, "' has mode 0 only, got ", mode);
+  TORCH_CHECK(a.dim() == 2, b.fn, ": argument 'a' of group_form = '", form,
+              "' must be [R,C], got sizes=", a.sizes());
+  TORCH_CHECK(a.size(0) % 64 == 0 && a.size(1) % 64 == 0 && a.size(0) / 64 <= 65535, b.fn,
+              ": argument 'a' of group_form = '", form,
+              "' needs R % 64 == 0, C % 64 == 0 and R < 2^22, got sizes=", a.sizes());
+  b.arg("a", a, BF16);
+  gemm_grouped_aligned(b, "a", a);
+}
+
+// group_form = "fp8_amax": a [R,C] bf16 -> fp32 [1] = max |a|
+at::Tensor fp8_amax(const Binding& b, const at::Tensor& a, const Weights& bw, int64_t mode) {
+  fp8_one_operand(b, "fp8_amax", a, bw, mode);
+  auto out = at::empty({1}, a.options().dtype(F32));
+  unsigned int* po = reinterpret_cast<unsigned int*>(out.data_ptr<float>());
+  b.launch(fp8_amax_clear, 1, 1, po);
+  const int64_t n8 = a.numel() / 8;
+  if (n8 > 0)
+    b.launch(fp8_amax_bf16, grid_for(n8, F8Q_AMAX_THREADS), F8Q_AMAX_THREADS, bf16(a), po, n8);
+  return out;
+}
+
+// group_form = "fp8_quantize": a [R,C] bf16, scale_a fp32 [1] -> group_out
+// [R,C] and / or out_t [C,R], both of one fp8 dtype
+at::Tensor fp8_quantize(const Binding& b, const at::Tensor& a, const Weights& bw, int64_t mode,
+                        const OptTensor& scale, const OptTensor& q, const OptTensor& qt) {
+  fp8_one_operand(b, "fp8_quantize", a, bw, mode);
+  TORCH_CHECK(scale.has_value(), b.fn, ": argument 'scale_a' expected dtype=Float sizes=[1] ",
+              "with group_form = 'fp8_quantize'; got None");
+  TORCH_CHECK(q.has_value() || qt.has_value(), b.fn,
+              ": group_form = 'fp8_quantize' needs group_out, out_t or both");
+  const int64_t R = a.size(0), C = a.size(1);
+  b.arg("scale_a", scale, F32, {1});
+  const at::Tensor& first = q.has_value() ? *q : *qt;
+  const Dtypes dt = is_fp8(first) ? Dtypes(first.scalar_type()) : Dtypes(E4M3, E5M2);
+  b.arg("group_out", q, dt, {R, C});
+  b.arg("out_t", qt, dt, {C, R});
+  if (q.has_value()) gemm_grouped_aligned(b, "group_out", *q);
+  if (qt.has_value()) gemm_grouped_aligned(b, "out_t", *qt);
+  if (R == 0 || C == 0) return first;
+  b.launch(first.scalar_type() == E4M3 ? fp8_quantize_e4m3 : fp8_quantize_e5m2,
+           dim3((unsigned)(C / 64), (unsigned)(R / 64)), WAVE, bf16(a), scale->data_ptr<float>(),
+           u8_mut(q), u8_mut(qt), (int)R, (int)C);
+  return first;
+}
+
+// a fp8 [M,K] (e4m3 | e5m2), b e4m3 [N,K] -> bf16 [M,N] = a @ b^T * scale_a * scale_b
+at::Tensor gemm_fp8(const Binding& bd, const at::Tensor& a, const Weights& bw, int64_t mode,
+                    const OptTensor& scale_a, const OptTensor& scale_b) {
+  TORCH_CHECK(std::holds_alternative<at::Tensor>(bw), bd.fn,
+              ": b is a list of tensors only with group_form");
+  const at::Tensor& b = std::get<at::Tensor>(bw);
+  TORCH_CHECK(mode == 0, bd.fn, ": mode = ", mode, " must be 0 with fp8 operands");
+  for (const char* name : {"scale_a", "scale_b"})
+    TORCH_CHECK((name[6] == 'a' ? scale_a : scale_b).has_value(), bd.fn, ": argument '", name,
+                "' expected dtype=Float sizes=[1] with fp8 operands; got None");
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2, bd.fn, ": a and b must be 2-D, got a sizes=",
+              a.sizes(), " b sizes=", b.sizes());
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && M <= INT_MAX && N <= INT_MAX && K <= INT_MAX,
+              bd.fn, ": M, N, K must be >= 1 and fit int");
+  TORCH_CHECK(M % F8_BM == 0 && N % F8_BN == 0 && K % F8_BK == 0, bd.fn,
+              " tile divisibility violated: fp8 operands require M % ", F8_BM, " == 0, N % ",
+              F8_BN, " == 0 and K % ", F8_BK, " == 0, got M = ", M, ", N = ", N, ", K = ", K);
+  bd.arg("a", a, Dtypes(E4M3, E5M2));
+  bd.arg("b", b, E4M3, {N, K});
+  bd.arg("scale_a", scale_a, F32, {1});
+  bd.arg("scale_b", scale_b, F32, {1});
+  gemm_grouped_aligned(bd, "a", a);
+  gemm_grouped_aligned(bd, "b", b);
+  auto c = at::empty({M, N}, a.options().dtype(BF16));
+  bd.launch(a.scalar_type() == E4M3 ? gemm_fp8_tn_e4m3 : gemm_fp8_tn_e5m2,
+            dim3((unsigned)(M / F8_BM), (unsigned)(N / F8_BN), 1), F8_THREADS,
+            reinterpret_cast<const unsigned char*>(a.const_data_ptr()),
+            reinterpret_cast<const unsigned char*>(b.const_data_ptr()), bf16_mut(c),
+            scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), (int)M, (int)N, (int)K);
+  return c;
+}
+
 at::Tensor gemm_tn8(at::Tensor a, Weights bw, int64_t mode, OptTensor group_offsets,
-                    std::string group_form, OptTensor group_x, OptTensor group_out) {
+                    std::string group_form, OptTensor group_x, OptTensor group_out,
+                    OptTensor scale_a, OptTensor scale_b, OptTensor out_t) {
   // via the 8-phase 256x256 template (gemm8.hip); with group_form, the
-  // grouped expert forms (gemm_grouped.hip)
+  // grouped expert forms (gemm_grouped.hip), the transposing copy or the fp8
+  // quantisers; with fp8 operands, the fp8 GEMM (gemm_fp8.hip)
   Binding bd("gemm_tn8", "a", a);
   TORCH_CHECK(mode >= 0 && mode <= 8, "gemm_tn8: mode = ", mode, " must be in 0..8");
+  if (group_form == "fp8_amax" || group_form == "fp8_quantize") {
+    TORCH_CHECK(!group_offsets.has_value() && !group_x.has_value() && !scale_b.has_value(),
+                "gemm_tn8: group_form = '", group_form,
+                "' takes no group_offsets, group_x or scale_b");
+    if (group_form == "fp8_quantize")
+      return fp8_quantize(bd, a, bw, mode, scale_a, group_out, out_t);
+    TORCH_CHECK(!scale_a.has_value() && !group_out.has_value() && !out_t.has_value(),
+                "gemm_tn8: group_form = 'fp8_amax' takes no scale_a, group_out or out_t");
+    return fp8_amax(bd, a, bw, mode);
+  }
+  TORCH_CHECK(!out_t.has_value(), "gemm_tn8: out_t belongs to group_form = 'fp8_quantize'");
+  const bool known_form = group_form.empty() || group_form == "transpose" ||
+                          group_form == "fwd" || group_form == "dgrad" || group_form == "wgrad";
+  const bool fp8 = group_form.empty() && is_fp8(a);
+  // (an unknown group_form is reported as such by gemm_grouped)
+  TORCH_CHECK(!known_form || fp8 || (!scale_a.has_value() && !scale_b.has_value()),
+              "gemm_tn8: scale_a and scale_b belong to fp8 operands without group_form, or to ",
+              "group_form = 'fp8_quantize'");
   if (group_form == "transpose") return gemm_operand_t(bd, a, bw, mode);
   if (!group_form.empty() || group_offsets.has_value() || group_x.has_value() ||
       group_out.has_value())
     return gemm_grouped(bd, a, bw, group_offsets, group_form, group_x, group_out);
+  if (fp8) return gemm_fp8(bd, a, bw, mode, scale_a, scale_b);
   TORCH_CHECK(std::holds_alternative<at::Tensor>(bw),
               "gemm_tn8: b is a list of tensors only with group_form");
   const at::Tensor& b = std::get<at::Tensor>(bw);
@@ -1092,7 +1209,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_tn", &gemm_tn, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("variant") = 0);
   m.def("gemm_tn8", &gemm_tn8, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("mode") = 0,
         pybind11::arg("group_offsets") = pybind11::none(), pybind11::arg("group_form") = "",
-        pybind11::arg("group_x") = pybind11::none(), pybind11::arg("group_out") = pybind11::none());
+        pybind11::arg("group_x") = pybind11::none(), pybind11::arg("group_out") = pybind11::none(),
+        pybind11::arg("scale_a") = pybind11::none(), pybind11::arg("scale_b") = pybind11::none(),
+        pybind11::arg("out_t") = pybind11::none());
   m.def("fa_bwd", &fa_bwd);
   m.def("fa_bwd2", &fa_bwd2, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
         pybind11::arg("o"), pybind11::arg("dout"), pybind11::arg("lse"),
